@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark: pair comparisons/s of the sharded AUC U-statistic (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K headline steps and prints the headline's JSON line
+(metric, value, ms_per_step, its live roofline).  --full adds every other line to it: the same
+steps on the other count paths, the incomplete statistic, the strong/weak scaling forms, the
+one-shard and drop-in calls, the SGD lines with their trade-off curve and the CPU baselines.
+--dump-outputs DIR writes what the timed call returned and left behind (the K estimates and the
+sample's final arrays) as DIR/<name>.npy; the inputs are the same in every run of the same
+arguments, so two builds can be compared output for output.
 
 Workload (BASELINE.json configs[2]): n = 1e6 X-scores and 1e6 Z-scores (float64, synthetic
 N(0.5,1) / N(0,1)) resident in HBM, cut into N = 64 prop-SWOR shards of 15625 x 15625 pairs —
@@ -146,6 +154,14 @@ def parse():
                     help="untimed steps before the warmup, until the GPU clock is steady")
     ap.add_argument("--incomplete-B", type=int, default=1_000_000,
                     help="pairs per shard of the incomplete-statistic line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other line (other count paths, "
+                         "incomplete statistic, scaling forms, SGD lines, CPU baselines); the "
+                         "--no-* options below narrow such a run and do nothing without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed call's outputs (the K estimates, the sample's final "
+                         "X and Z) as DIR/<name>.npy, float64, at most 64 MB in all (a fixed "
+                         "seeded sample of larger arrays)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sgd", action="store_true", help="skip the SGD steps/s secondary")
     ap.add_argument("--no-strong", action="store_true",
@@ -1006,6 +1022,28 @@ def weak_c3(args, group, rank, world, span, torch):
             "shards_per_gpu": N_SHARDS, "estimate_last_step": float(ests[-1])}
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(path, rank, world, ests, X, Z):
+    """--dump-outputs: what the timed UnN_many call gave its caller, as float64 .npy files:
+    estimates.npy (the K values it returned, the last step's last; rank 0 writes it) and the
+    sample's arrays as the call's last repartition left them, X.npy and Z.npy (X_rank<r>.npy /
+    Z_rank<r>.npy over several ranks, each rank its own elements).  Arrays that would not fit
+    DUMP_BYTES in all are cut to a fixed seeded sample of their elements, in index order."""
+    d = pathlib.Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    if rank == 0:
+        np.save(d / "estimates.npy", np.asarray(ests, dtype=np.float64))
+    m = (DUMP_BYTES - 8 * len(ests)) // (2 * world * 8) - 64  # elements per array, headers aside
+    for name, a in (("X", X), ("Z", Z)):
+        a = a.detach().cpu().numpy().astype(np.float64, copy=False)
+        if a.size > m:
+            a = a[np.sort(np.random.RandomState(64).choice(a.size, m, replace=False))]
+        np.save(d / f"{name}{sfx}.npy", a)
+
+
 def main():
     args = parse()
     world = resolve_world(args)
@@ -1102,6 +1140,15 @@ def main():
     # one untimed run at the timed run's length first: the first K-step UnN_many of a process
     # ran ~7 % slower than the later ones at K = 100 (tools/bench_bisect.py)
     S.UnN_many(range(40_000, 40_000 + args.steps))
+    # the settle steps run on a copy of the sample: their number depends on the clock of the
+    # day, and every step repartitions the sample it runs on, so on S they would make the timed
+    # call's inputs (and --dump-outputs) differ from run to run.  One settle call on S itself
+    # first: a sample's second call is its first with carried images and sets up what those need
+    # (a pinned host word, a side stream), which must not happen right before the timed call —
+    # the GPU idles meanwhile and its clock drops (the count ran at 0.88 of peak instead of 0.95
+    # at K = 20)
+    S.UnN_many(range(20_000, 20_005))
+    S_settle = ShardedSample(S.X.clone(), S.Z.clone(), shards, group=group, algo="pairs")
     # the process's objects so far (torch's import, the sample, the pools) into the cyclic
     # collector's permanent generation: its passes inside a timed call then scan only the
     # call's own young objects (a 2e6-object heap cost a K = 20 call ~0.15 ms of host time,
@@ -1113,7 +1160,7 @@ def main():
     gc.freeze()
     t_s = time.perf_counter()
     while True:
-        S.UnN_many(range(20_000, 20_005))
+        S_settle.UnN_many(range(20_000, 20_005))
         go = time.perf_counter() - t_s < args.settle_ms * 1e-3
         if group is not None:  # rank 0 decides, so every rank runs the same collectives
             flag = torch.tensor([int(go)], dtype=torch.int64, device="cuda")
@@ -1149,6 +1196,114 @@ def main():
         kms = chain_ms.ms_per_unit()
     emit_step_ms = emit_ms.ms_per_unit() if chain_path else None
     rank_call_ms = float(np.mean([a.elapsed_time(b) for a, b in rank_ms.used()] or [0.0]))
+    if args.dump_outputs:  # before any other line reuses the sample
+        dump_outputs(args.dump_outputs, rank, world, ests, S.X, S.Z)
+
+    count_kernel = ("k_count_chain" if chain_path else "k_count_rank" if rank_path
+                    else "k_count_complete")
+    traffic, traffic_plain = pmc_traffic(count_kernel)
+    total_pairs = pairs_per_step_rank * world * args.steps
+    value = total_pairs / dt
+    achieved = pairs_per_step_rank / (kms * 1e-3)  # lane-ops/s, 1 compare per pair (strict)
+    out = {
+        "metric": "pair comparisons/sec (node) for sharded AUC U-stat at n=1e6/class (UnN, "
+                  "N=64 prop-SWOR shards, device repartition each step)",
+        "value": value,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle_ms": args.settle_ms,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic: X~N(0.5,1), Z~N(0,1) float64 scores generated on the device",
+        "config": {"workload": "UnN sharded complete AUC U-statistic (estimation-experiment/"
+                               "main.py:72-74) + device repartition per step, K steps as "
+                               "est.UnNT's loop (BASELINE configs[2])",
+                   "repartition": ("device keyed Feistel permutation per step (a device-RNG "
+                                   "stand-in for np.random.shuffle, pinned against the oracle's "
+                                   "restatement and validated statistically, DESIGN.md §4.5); "
+                                   "the NumPy-order drop-in path is the drop_in_C3 line of a "
+                                   "--full run"),
+                   "n_per_class_total": n * world if args.scaling == "weak" else args.n,
+                   "shards_total": shards * world,
+                   "n_per_class_per_gpu": n, "shards_per_gpu": shards,
+                   "pairs_per_step_per_gpu": pairs_per_step_rank,
+                   "parallelism": (f"dp{world}: shards over ranks, "
+                                   + ("RCCL" if os.environ.get("TW_BENCH_BACKEND", "nccl")
+                                      == "nccl" else "gloo (rehearsal)")
+                                   + (" step chains: all-gather of the sample once per call, "
+                                      "each rank walks its own elements' repartitions, one "
+                                      "all-to-all of {image, position} records per chunk of "
+                                      "<= 32 steps, every step of a chunk counted in one launch"
+                                      if S._chain_ok() else " all-to-all repartition")
+                                   + " + all-reduce of counts"
+                                   if world > 1 else
+                                   ("dp1: one GPU; step chains: every element walks the K "
+                                    "repartitions (k_chain_emit, one launch per chunk of <= 32 "
+                                    "steps) and one k_count_chain launch counts every shard of "
+                                    "the chunk's steps"
+                                    + (" — RCCL world-size-1 rehearsal: every multi-rank "
+                                       "collective forced" if S.coll else "")))},
+        "roofline": {"bound": "valu", "kernel": count_kernel,
+                     "achieved": achieved / 1e12, "peak": PEAK_LANE_OPS / 1e12,
+                     "unit": "Tlane-op/s", "frac": achieved / PEAK_LANE_OPS,
+                     # the same launches under rocprofv3 --kernel-trace (committed summary)
+                     "frac_traced": traced_count_chain(args.steps) if chain_path else None,
+                     "count_kernel_ms": kms, "traffic": traffic,
+                     "traffic_count_only": traffic_plain,
+                     "traffic_unit": ("HBM bytes per step: the chunk's k_count_chain launch / its "
+                                      "steps" if chain_path else "HBM bytes per launch"),
+                     "traffic_emit_per_step": pmc_emit_traffic() if chain_path else None,
+                     # the count reads each step's 4-B images of its n + n scores once
+                     "algorithmic_bytes_per_step": (4 * 2 * n if chain_path
+                                                    else None),
+                     "traffic_source": ("rocprofv3 --pmc FETCH_SIZE+WRITE_SIZE of this kernel "
+                                        "at the one-GPU shape (profiles/*count_pmc*.json), "
+                                        "not measured at this run's per-rank shape"
+                                        if world > 1 else
+                                        "rocprofv3 --pmc FETCH_SIZE+WRITE_SIZE of this kernel "
+                                        "at this shape (profiles/*count_pmc*.json)"),
+                     "ranking_ms_per_call": rank_call_ms if rank_path or chain_path else None,
+                     "chain_count_launch_ms": chain_launch_ms if chain_path else None,
+                     "chain_emit_ms_per_step": emit_step_ms,
+                     "note": ("1 compared pair = 1 lane-op of the contract (f64 vector "
+                              "lane-op peak); the count compares packed f32 rank images of "
+                              "the scores (two pairs per lane per instruction: a clamped "
+                              "v_pk_add_f32 and an accumulating one), exact by construction; "
+                              "the ranking of X u Z runs in a sample's first UnN_many call; "
+                              "later calls carry the images of the final arrays "
+                              "(device.CARRY_IMAGES: the timed call, ranking_ms_per_call = 0; "
+                              "first_call_ranking, a --full line, times the same steps with "
+                              "the ranking) "
+                              if rank_path or chain_path else "1 v_cmp_f64 lane-op per pair; ")
+                             + ("step chains (csrc/chain.hip): every element walks the call's "
+                                "repartitions once (k_chain_emit, chain_emit_ms_per_step) and "
+                                "ONE k_count_chain launch counts all steps of a chunk "
+                                "(chain_count_launch_ms); count_kernel_ms = that launch per "
+                                "step; traffic = HBM bytes per step of the count launch "
+                                "(FETCH_SIZE+WRITE_SIZE) from the committed rocprofv3 --pmc "
+                                "summary" if chain_path else
+                                "the timed launch also carries the next repartition on its tail "
+                                "blocks; traffic = HBM bytes/launch (FETCH_SIZE+WRITE_SIZE) from "
+                                "the committed rocprofv3 --pmc summary of this kernel: the timed "
+                                "launch, and a launch without the repartition")},
+        "estimate_last_step": float(est),
+        "full": bool(args.full),
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if group is not None:
+            barrier()  # rank 0's CPU baselines run after every rank's GPU work
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the headline alone
+        return finish()
 
     # the same K steps as a sample's FIRST call: the ranking inside the call (the timed call
     # above carries the images of the previous call's final arrays, device.CARRY_IMAGES —
@@ -1338,100 +1493,10 @@ def main():
     progress("plumbing C1")
     c1 = plumbing_C1(rank == 0 and world == 1 and not args.no_cpu_baseline)
 
-    count_kernel = ("k_count_chain" if chain_path else "k_count_rank" if rank_path
-                    else "k_count_complete")
-    traffic, traffic_plain = pmc_traffic(count_kernel)
-    total_pairs = pairs_per_step_rank * world * args.steps
-    value = total_pairs / dt
-    achieved = pairs_per_step_rank / (kms * 1e-3)  # lane-ops/s, 1 compare per pair (strict)
-    out = {
-        "metric": "pair comparisons/sec (node) for sharded AUC U-stat at n=1e6/class (UnN, "
-                  "N=64 prop-SWOR shards, device repartition each step)",
-        "value": value,
-        "unit": "pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "settle_ms": args.settle_ms,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic: X~N(0.5,1), Z~N(0,1) float64 scores generated on the device",
-        "config": {"workload": "UnN sharded complete AUC U-statistic (estimation-experiment/"
-                               "main.py:72-74) + device repartition per step, K steps as "
-                               "est.UnNT's loop (BASELINE configs[2])",
-                   "repartition": ("device keyed Feistel permutation per step (a device-RNG "
-                                   "stand-in for np.random.shuffle, pinned against the oracle's "
-                                   "restatement and validated statistically, DESIGN.md §4.5); "
-                                   "the NumPy-order drop-in path is the drop_in_C3 line"),
-                   "n_per_class_total": n * world if args.scaling == "weak" else args.n,
-                   "shards_total": shards * world,
-                   "n_per_class_per_gpu": n, "shards_per_gpu": shards,
-                   "pairs_per_step_per_gpu": pairs_per_step_rank,
-                   "parallelism": (f"dp{world}: shards over ranks, "
-                                   + ("RCCL" if os.environ.get("TW_BENCH_BACKEND", "nccl")
-                                      == "nccl" else "gloo (rehearsal)")
-                                   + (" step chains: all-gather of the sample once per call, "
-                                      "each rank walks its own elements' repartitions, one "
-                                      "all-to-all of {image, position} records per chunk of "
-                                      "<= 32 steps, every step of a chunk counted in one launch"
-                                      if S._chain_ok() else " all-to-all repartition")
-                                   + " + all-reduce of counts"
-                                   if world > 1 else
-                                   ("dp1: one GPU; step chains: every element walks the K "
-                                    "repartitions (k_chain_emit, one launch per chunk of <= 32 "
-                                    "steps) and one k_count_chain launch counts every shard of "
-                                    "the chunk's steps"
-                                    + (" — RCCL world-size-1 rehearsal: every multi-rank "
-                                       "collective forced" if S.coll else "")))},
-        "roofline": {"bound": "valu", "kernel": count_kernel,
-                     "achieved": achieved / 1e12, "peak": PEAK_LANE_OPS / 1e12,
-                     "unit": "Tlane-op/s", "frac": achieved / PEAK_LANE_OPS,
-                     # the same launches under rocprofv3 --kernel-trace (committed summary)
-                     "frac_traced": traced_count_chain(args.steps) if chain_path else None,
-                     "count_kernel_ms": kms, "traffic": traffic,
-                     "traffic_count_only": traffic_plain,
-                     "traffic_unit": ("HBM bytes per step: the chunk's k_count_chain launch / its "
-                                      "steps" if chain_path else "HBM bytes per launch"),
-                     "traffic_emit_per_step": pmc_emit_traffic() if chain_path else None,
-                     # the count reads each step's 4-B images of its n + n scores once
-                     "algorithmic_bytes_per_step": (4 * 2 * n if chain_path
-                                                    else None),
-                     "traffic_source": ("rocprofv3 --pmc FETCH_SIZE+WRITE_SIZE of this kernel "
-                                        "at the one-GPU shape (profiles/*count_pmc*.json), "
-                                        "not measured at this run's per-rank shape"
-                                        if world > 1 else
-                                        "rocprofv3 --pmc FETCH_SIZE+WRITE_SIZE of this kernel "
-                                        "at this shape (profiles/*count_pmc*.json)"),
-                     "ranking_ms_per_call": rank_call_ms if rank_path or chain_path else None,
-                     "chain_count_launch_ms": chain_launch_ms if chain_path else None,
-                     "chain_emit_ms_per_step": emit_step_ms,
-                     "note": ("1 compared pair = 1 lane-op of the contract (f64 vector "
-                              "lane-op peak); the count compares packed f32 rank images of "
-                              "the scores (two pairs per lane per instruction: a clamped "
-                              "v_pk_add_f32 and an accumulating one), exact by construction; "
-                              "the ranking of X u Z runs in a sample's first UnN_many call; "
-                              "later calls carry the images of the final arrays "
-                              "(device.CARRY_IMAGES: the timed call, ranking_ms_per_call = 0; "
-                              "first_call_ranking times the same steps with the ranking) "
-                              if rank_path or chain_path else "1 v_cmp_f64 lane-op per pair; ")
-                             + ("step chains (csrc/chain.hip): every element walks the call's "
-                                "repartitions once (k_chain_emit, chain_emit_ms_per_step) and "
-                                "ONE k_count_chain launch counts all steps of a chunk "
-                                "(chain_count_launch_ms); count_kernel_ms = that launch per "
-                                "step; traffic = HBM bytes per step of the count launch "
-                                "(FETCH_SIZE+WRITE_SIZE) from the committed rocprofv3 --pmc "
-                                "summary" if chain_path else
-                                "the timed launch also carries the next repartition on its tail "
-                                "blocks; traffic = HBM bytes/launch (FETCH_SIZE+WRITE_SIZE) from "
-                                "the committed rocprofv3 --pmc summary of this kernel: the timed "
-                                "launch, and a launch without the repartition")},
+    out.update({
         "first_call_ranking": fresh_line,
         "score_compare_kernel": score_line,
         "half_ties": half_line,
-        "estimate_last_step": float(est),
         "plumbing_C1": c1,
         "single_shard_C2": single,
         "sorted_count": ({
@@ -1512,7 +1577,7 @@ def main():
                                  "32-bit integer)"}},
         "incomplete_replay": inc_replay,
         "strong_C3": strong,
-    }
+    })
     # Every section after the headline runs guarded: an exception there is recorded in the line
     # ({"error": ...}) and ends the remaining sections, on every rank alike (over ranks the
     # ranks agree through one small all-reduce per section), so the headline is still printed
@@ -1641,11 +1706,7 @@ def main():
                                        "broadcast compare, 1 core); not rerun here (~23 s)")
             return d3
         out["drop_in_C3"] = guarded("drop_in_C3", drop_in, collective=False, independent=True)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if group is not None:
-        barrier()  # rank 0's CPU baselines run after every rank's GPU work
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -64,6 +64,48 @@ def test_spawn_ranks_failure(tmp_path):
     assert rc == 3  # rank 1's failure; rank 0 was stopped instead of waited for
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off unless given; --dump-outputs takes a directory."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """The timed call's outputs as float64 .npy files: whole where they fit, else the same
+    seeded sample of elements in every run, all files within the byte limit."""
+    import numpy as np
+    import torch
+    X = torch.arange(1000, dtype=torch.float64) * 0.5
+    Z = -torch.arange(1000, dtype=torch.float64)
+    ests = [0.25, 0.5, 0.75]
+    bench.dump_outputs(tmp_path / "a", 0, 1, ests, X, Z)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["X.npy", "Z.npy",
+                                                                  "estimates.npy"]
+    e = np.load(tmp_path / "a" / "estimates.npy")
+    assert e.dtype == np.float64 and e.tolist() == ests
+    assert np.array_equal(np.load(tmp_path / "a" / "X.npy"), X.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "Z.npy"), Z.numpy())
+    # a limit the arrays do not fit: a fixed sample, in index order, the same for X and Z
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 3 + 2 * 8 * (64 + 100))
+    st = np.random.get_state()[1].copy()
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, 0, 1, ests, X, Z)
+    assert np.array_equal(np.random.get_state()[1], st)  # the global RNG is left alone
+    xb, zb = np.load(tmp_path / "b" / "X.npy"), np.load(tmp_path / "b" / "Z.npy")
+    assert xb.shape == zb.shape == (100,) and np.all(np.diff(xb) > 0)
+    assert np.array_equal(xb * -2, zb) and np.isin(xb, X.numpy()).all()
+    assert np.array_equal(xb, np.load(tmp_path / "c" / "X.npy"))
+    size = sum(p.stat().st_size for p in (tmp_path / "b").iterdir())
+    assert size <= bench.DUMP_BYTES
+    # several ranks: each its own files, the estimates once
+    bench.dump_outputs(tmp_path / "r", 1, 2, ests, X, Z)
+    assert sorted(p.name for p in (tmp_path / "r").iterdir()) == ["X_rank1.npy", "Z_rank1.npy"]
+
+
 def test_bench_rejects_mismatched_world():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=env,

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $O/${R}_gpu_tests.log
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/${R}_smoke.log 2>&1
 tail -1 $O/${R}_smoke.log
-timeout -k 10 400 python -u bench.py > $O/${R}_bench.json 2> $O/${R}_bench.err
+timeout -k 10 400 python -u bench.py --full > $O/${R}_bench.json 2> $O/${R}_bench.err
 tail -c 600 $O/${R}_bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_trace -o run \
   -- python3 bench.py --steps 20 --warmup 1 --no-cpu-baseline --no-sgd > $O/${R}_trace.log 2>&1
