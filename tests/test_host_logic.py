@@ -170,3 +170,107 @@ def test_learning_engine_device_selection(monkeypatch):
     assert f(None, 256, 100, 512, None, "replicated", "incomplete") is None
     assert f(None, 256, 4096, 512, None, "replicated", "incomplete") == list(range(8))
     assert f(None, 100, 4096, 512, None, "replicated", "incomplete") == [0, 1, 2, 3, 4]
+
+
+# ------------------------------------------------------------------ the dtype contract's host side
+def _dtype_cells(group):
+    from golden import dtype_cells as DC
+    return [c.id for c in DC.CELLS if c.group == group and c.stored]
+
+
+@pytest.fixture(scope="module")
+def dtype_fixtures():
+    from golden import dtype_cells as DC
+    return DC, DC.load_index(), DC.load_arrays()
+
+
+@pytest.mark.parametrize("cid", [c for c in _dtype_cells("comparisons") if c.endswith("/est.Un")])
+def test_compare_operands_over_the_dtype_matrix(tw, dtype_fixtures, cid):
+    """The int64 / float64 keys order every pair of the matrix's inputs as NumPy's own
+    comparison does (uint64 against int64 exactly, float64 against int64 rounded)."""
+    from tuplewise import _engine as E
+    DC, index, arrays = dtype_fixtures
+    X, Z = arrays[f"{cid}/X"], arrays[f"{cid}/Z"]
+    x, z, code = E.compare_operands(X, Z)
+    assert x.dtype == z.dtype and x.dtype in (np.int64, np.float64)
+    for op in (np.greater, np.equal):
+        assert np.array_equal(op(x.reshape(-1, 1), z.reshape(1, -1)),
+                              op(X.reshape(-1, 1), Z.reshape(1, -1))), op
+
+
+@pytest.mark.parametrize("cid", [c for c in _dtype_cells("float kernels")
+                                 if "UnN" not in c and "UB_indices" not in c])
+def test_float_kernel_operands_over_the_dtype_matrix(tw, dtype_fixtures, cid):
+    """float_kernel_operands either raises what the contract names, or hands the device
+    doubles on which the kernel's float64 formula gives the reference's value."""
+    from tuplewise import _engine as E, _lib as L
+    DC, index, arrays = dtype_fixtures
+    cell = DC.BY_ID[cid]
+    X, Z = arrays[f"{cid}/X"], arrays[f"{cid}/Z"]
+    kern = {"prod": L.TW_KERN_PROD, "gini": L.TW_KERN_GINI}.get(cell.args.get("kernel"),
+                                                                 L.TW_KERN_HINGE)
+    margin = float(cell.args.get("margin", 0))
+    if cell.contract not in DC.RTOL:
+        with pytest.raises({"TypeError": TypeError,
+                            "NotImplementedError": NotImplementedError}[cell.contract]):
+            E.float_kernel_operands(X, Z, kern, margin)
+        return
+    x, z = E.float_kernel_operands(X, Z, kern, margin)
+    assert x.dtype == z.dtype == np.float64
+    xc, zr = x.reshape(-1, 1), z.reshape(1, -1)
+    terms = {L.TW_KERN_PROD: xc * zr, L.TW_KERN_GINI: np.abs(xc - zr),
+             L.TW_KERN_HINGE: np.maximum(zr - xc + margin, 0)}[kern]
+    np.testing.assert_allclose(terms.mean(), arrays[f"{cid}/value"],
+                               rtol=DC.RTOL[cell.contract], atol=0)
+
+
+def test_float_kernel_operands_names_the_dtype(tw):
+    from tuplewise import _engine as E, _lib as L
+    with pytest.raises(NotImplementedError, match="uint8"):
+        E.float_kernel_operands(np.array([1, 200], np.uint8), np.array([2, 3], np.uint8),
+                                L.TW_KERN_GINI)
+    with pytest.raises(NotImplementedError, match="float16"):
+        E.float_kernel_operands(np.ones(2, np.float16), np.ones(2, np.int8), L.TW_KERN_PROD)
+    E.float_kernel_operands(np.ones(2, np.float16), np.ones(2), L.TW_KERN_PROD)  # in float64
+    E.float_kernel_operands(np.array([200, 3], np.uint8), np.array([2, 3], np.uint8),
+                            L.TW_KERN_GINI)  # x >= z everywhere: nothing wraps
+    with pytest.raises(NotImplementedError):  # abs(-2^63) wraps too
+        E.float_kernel_operands(np.array([-2 ** 62], np.int64), np.array([2 ** 62], np.int64),
+                                L.TW_KERN_GINI)
+    with pytest.raises(NotImplementedError):  # 126 - 0 fits int8, + 2 does not
+        E.float_kernel_operands(np.array([0], np.int8), np.array([126], np.int8),
+                                L.TW_KERN_HINGE, 2.0)
+
+
+def test_check_index_refuses_what_numpy_refuses(tw):
+    from tuplewise.compute_stats import _check_index
+    assert np.array_equal(_check_index(np.array([0, -1, 3], np.int32), 5), [0, 4, 3])
+    assert _check_index(np.array([7], np.uint8), 8).dtype == np.int64
+    for bad in (np.array([1.0]), np.array([2 ** 63], np.uint64), np.array([2 ** 64 - 1], np.uint64),
+                np.array([5]), np.array([-6])):
+        with pytest.raises(IndexError):
+            _check_index(bad, 5)
+    with pytest.raises(NotImplementedError):
+        _check_index(np.array([True, False]), 2)
+
+
+@pytest.mark.parametrize("which", ["X", "Z"])
+def test_shuffle_pair_read_only_is_numpy_s(tw, which):
+    """A read-only array is np.random.shuffle's ValueError, with the arrays before it shuffled
+    and the RNG advanced exactly as the reference's two calls leave them."""
+    from tuplewise.numpy_rng import shuffle_pair
+
+    def run(shuffle):
+        X, Z = np.arange(20.0), np.arange(30.0)
+        (X if which == "X" else Z).setflags(write=False)
+        np.random.seed(3)
+        with pytest.raises(ValueError):
+            shuffle(X, Z)
+        return X, Z, np.random.randint(0, 2 ** 31 - 1)
+
+    def reference(X, Z):
+        np.random.shuffle(X)
+        np.random.shuffle(Z)
+
+    for a, b in zip(run(shuffle_pair), run(reference)):
+        assert np.array_equal(a, b)

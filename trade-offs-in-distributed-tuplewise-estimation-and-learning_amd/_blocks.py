@@ -264,6 +264,14 @@ class CompleteCount(BlockSpec):
         return list(counts.astype(np.float64) / pairs.astype(np.float64))
 
 
+def _mean_type(X, Z):
+    """The type of NumPy's mean of a float kernel's terms: the operands' float type (float32
+    stays float32; the device accumulates in float64, so a float32 result is the
+    better-rounded value), float64 for integer and bool terms."""
+    rt = np.result_type(np.asarray(X).dtype, np.asarray(Z).dtype)
+    return rt.type if rt.kind == "f" else np.float64
+
+
 class CompleteSum(BlockSpec):
     """cs.Un prod/gini (compute_stats.py:15-18) and conv_AUC (compute_stats.py:129-135):
     mean over all pairs of a float kernel."""
@@ -273,8 +281,7 @@ class CompleteSum(BlockSpec):
         self.margin = margin
 
     def evaluate(self, X, Z, blocks):
-        x = _flat(X).astype(np.float64, copy=False)
-        z = _flat(Z).astype(np.float64, copy=False)
+        x, z = E.float_kernel_operands(_flat(X), _flat(Z), self.kern, self.margin)
         blocks = _elements(_elements(blocks, "x", _row_size(X)), "z", _row_size(Z))
         if M.slots_for(sum(b.nx() * b.nz() for b in blocks), len(blocks)):
             def enqueue(sub):
@@ -290,10 +297,7 @@ class CompleteSum(BlockSpec):
             za, zo = _layout(zd, blocks, "z")
             sums = E.pair_sum_complete(E.Shards(xa, xo, za, zo, L.TW_F64), self.kern,
                                        self.margin)
-        # NumPy returns the mean in the operands' float type (float32 stays float32); the
-        # device accumulates in float64, so float32 results are the better-rounded value.
-        rt = np.result_type(np.asarray(X).dtype, np.asarray(Z).dtype)
-        cast = rt.type if rt.kind == "f" else np.float64
+        cast = _mean_type(X, Z)
         return [cast(s / np.float64(b.nx() * b.nz())) for b, s in zip(blocks, sums)]
 
     def evaluate_device(self, xd, zd, blocks):
@@ -368,8 +372,8 @@ def block_indexed_values(x: np.ndarray, z: np.ndarray, blocks: list, ix_loc: lis
     if kernel == "AUC":
         xx, zz, code, mode = E.subtract_gt_operands(x, z)
     else:
-        xx, zz, code, mode = (x.astype(np.float64, copy=False), z.astype(np.float64, copy=False),
-                              L.TW_F64, None)
+        kern = {"prod": L.TW_KERN_PROD, "gini": L.TW_KERN_GINI}[kernel]
+        (xx, zz), code, mode = E.float_kernel_operands(x, z, kern), L.TW_F64, None
     npairs = np.diff(offs)
     if mode != "ne" and M.slots_for(int(offs[-1]) * 50, len(blocks)):  # ~50 compares a pair
         pos = {id(b): i for i, b in enumerate(blocks)}
@@ -393,7 +397,8 @@ def block_indexed_values(x: np.ndarray, z: np.ndarray, blocks: list, ix_loc: lis
         vals = M.gather(M.spread(blocks, lambda b: npairs[pos[id(b)]], enqueue))
         if kernel == "AUC":
             return [E.ratio(c, p) for c, p in zip(vals.astype(np.int64).view(np.uint64), npairs)]
-        return [np.float64(v / np.float64(p)) for v, p in zip(vals, npairs)]
+        cast = _mean_type(x, z)
+        return [cast(v / np.float64(p)) for v, p in zip(vals, npairs)]
     xa, xo = _layout(L.to_device(xx), blocks, "x")
     za, zo = _layout(L.to_device(zz), blocks, "z")
     ix = np.concatenate([a + o for a, o in zip(ix_loc, xo[:-1])]) if ix_loc else np.zeros(0, np.int64)
@@ -404,7 +409,8 @@ def block_indexed_values(x: np.ndarray, z: np.ndarray, blocks: list, ix_loc: lis
         return [E.ratio(c, p) for c, p in zip(counts, npairs)]
     kern = {"prod": L.TW_KERN_PROD, "gini": L.TW_KERN_GINI}[kernel]
     sums = E.pair_sum_indexed(xa, za, ix, iz, offs, kern)
-    return [np.float64(s / np.float64(p)) for s, p in zip(sums, npairs)]
+    cast = _mean_type(x, z)
+    return [cast(s / np.float64(p)) for s, p in zip(sums, npairs)]
 
 
 def indexed_values(x: np.ndarray, z: np.ndarray, ix: np.ndarray, iz: np.ndarray,
@@ -423,10 +429,11 @@ def indexed_values(x: np.ndarray, z: np.ndarray, ix: np.ndarray, iz: np.ndarray,
         return [E.ratio(c, p) for c, p in zip(counts, npairs)]
     kern = {"prod": L.TW_KERN_PROD, "gini": L.TW_KERN_GINI, "hinge": L.TW_KERN_HINGE,
             "logistic": L.TW_KERN_LOGISTIC}[kernel]
-    xd = L.to_device(x.astype(np.float64, copy=False))
-    zd = L.to_device(z.astype(np.float64, copy=False))
+    xx, zz = E.float_kernel_operands(x, z, kern, margin)
+    xd, zd = L.to_device(xx), L.to_device(zz)
     sums = E.pair_sum_indexed(xd, zd, ix, iz, pair_off, kern, margin)
-    return [np.float64(s / np.float64(p)) for s, p in zip(sums, npairs)]
+    cast = _mean_type(x, z)
+    return [cast(s / np.float64(p)) for s, p in zip(sums, npairs)]
 
 
 def plan_un(X, Z, N, spec, sampling_type, variant: str, shuffle=shuffle_pair) -> list:

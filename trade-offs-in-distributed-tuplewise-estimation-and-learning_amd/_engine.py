@@ -15,16 +15,38 @@ from . import _lib as L
 _INT64_MIN = np.int64(-(2 ** 63))
 
 
+# uint64 against int64, exactly, as int64 keys.  Across the two sides only three things
+# matter: a negative signed value is below every unsigned one, an unsigned value >= 2^63 is
+# above every signed one, and in between both are the same integers.  So the signed side is
+# clamped below at -1, the unsigned side above at 2^63; the clamped values meet no equal on the
+# other side, so `>`, `>=` and `==` across the sides are unchanged.  The union [-1, 2^63] has
+# one value too many for int64's upper half, hence the common shift by 2^62.
+def _unsigned_key(u: np.ndarray) -> np.ndarray:
+    u = np.minimum(u.astype(np.uint64, copy=False), np.uint64(2 ** 63))
+    return (u - np.uint64(2 ** 62)).view(np.int64)  # wraps below 2^62: the negative keys
+
+
+def _signed_key(s: np.ndarray) -> np.ndarray:
+    return np.maximum(s.astype(np.int64, copy=False), np.int64(-1)) - np.int64(2 ** 62)
+
+
 def compare_operands(X: np.ndarray, Z: np.ndarray):
     """Operands of NumPy's `X > Z` as (x, z, dtype code) with identical ordering.
 
     NumPy compares in np.result_type(X, Z): float kinds compare as float64 (exact for every
     float input), signed/bool integers as int64, uint64 vs uint64 as unsigned (mapped to int64
-    keys by flipping the sign bit, an order isomorphism), uint64 vs signed as float64.
+    keys by flipping the sign bit, an order isomorphism).  uint64 against a signed integer is
+    the exception: result_type says float64, but NumPy's comparison loops compare the two
+    integers exactly, so they never go through float64 here either (_unsigned_key /
+    _signed_key).
     """
     X = np.asarray(X)
     Z = np.asarray(Z)
     rt = np.result_type(X.dtype, Z.dtype)
+    if rt.kind == "f" and X.dtype.kind in "ui" and Z.dtype.kind in "ui":
+        if X.dtype.kind == "u":
+            return _unsigned_key(X), _signed_key(Z), L.TW_I64
+        return _signed_key(X), _unsigned_key(Z), L.TW_I64
     if rt.kind == "f":
         return X.astype(np.float64, copy=False), Z.astype(np.float64, copy=False), L.TW_F64
     if rt.kind in "bi":
@@ -74,6 +96,61 @@ def subtract_gt_operands(X: np.ndarray, Z: np.ndarray):
         raise NotImplementedError(
             f"(X - Z) > 0 wraps in {rt}; only int64 wrap-around is reproduced on the device")
     raise TypeError(f"unsupported dtypes for X - Z: {X.dtype}, {Z.dtype}")
+
+
+_EXACT = 2 ** 53  # every integer up to this magnitude is a double
+
+
+def float_kernel_operands(X: np.ndarray, Z: np.ndarray, kern: int, margin: float = 0.0):
+    """(x, z) as float64 for the float kernels — prod `x * z` (compute_stats.py:16, :27), gini
+    `|x - z|` (:18, :29), hinge / logistic `phi(z - x + margin)` (:134, :143) — where the
+    device's float64 arithmetic gives what NumPy computes in rt = np.result_type(X, Z):
+
+      float64, float32 -> as they are (float32 accumulates in float32 in NumPy, in float64 here)
+      integers -> NumPy computes every term in rt, wrapping around, and averages the terms as
+                  doubles.  The doubles path is the same numbers exactly when the extremes
+                  prove that no difference, product or `+ margin` leaves rt and that every
+                  operand and term is within 2^53; else NotImplementedError.
+      bool     -> prod is `x and z`, which 0.0 / 1.0 products reproduce; NumPy has no boolean
+                  subtract, so gini / hinge / logistic raise its TypeError.
+      float16, longdouble -> NotImplementedError (their rounding is not reproduced).
+    The check reads the whole arrays' extremes: it can refuse a call whose own pairs would not
+    have wrapped, never pass one that does."""
+    X = np.asarray(X)
+    Z = np.asarray(Z)
+    rt = np.result_type(X.dtype, Z.dtype)
+    name = {L.TW_KERN_PROD: "prod", L.TW_KERN_GINI: "gini", L.TW_KERN_HINGE: "hinge",
+            L.TW_KERN_LOGISTIC: "logistic"}[kern]
+    if rt.kind == "b":
+        if kern != L.TW_KERN_PROD:
+            raise TypeError("numpy boolean subtract, the `-` operator, is not supported")
+    elif rt.kind == "f":
+        if rt.itemsize not in (4, 8):
+            raise NotImplementedError(
+                f"the {name} kernel on {rt} inputs: only float32 and float64 arithmetic is "
+                f"reproduced on the device")
+    elif rt.kind in "iu":
+        if X.size and Z.size:
+            info = np.iinfo(rt)
+            xlo, xhi, zlo, zhi = int(X.min()), int(X.max()), int(Z.min()), int(Z.max())
+            if kern == L.TW_KERN_PROD:
+                ends = [xlo * zlo, xlo * zhi, xhi * zlo, xhi * zhi]
+                terms = [(min(ends), max(ends))]
+            elif kern == L.TW_KERN_GINI:  # the difference, then its abs (abs(info.min) wraps)
+                terms = [(xlo - zhi, xhi - zlo), (0, max(0, zhi - xlo))]
+            else:
+                terms = [(zlo - xhi, zhi - xlo)]
+                if float(margin).is_integer():  # an integer margin is added in rt
+                    terms.append((zlo - xhi + int(margin), zhi - xlo + int(margin)))
+            ok = all(info.min <= lo and hi <= info.max and -_EXACT <= lo and hi <= _EXACT
+                     for lo, hi in terms + [(xlo, xhi), (zlo, zhi)])
+            if not ok:
+                raise NotImplementedError(
+                    f"the {name} kernel on {rt} inputs whose terms may wrap around in {rt} or "
+                    f"exceed 2^53: NumPy's integer arithmetic is not reproduced on the device")
+    else:
+        raise TypeError(f"unsupported dtypes for the {name} kernel: {X.dtype}, {Z.dtype}")
+    return X.astype(np.float64, copy=False), Z.astype(np.float64, copy=False)
 
 
 # ----------------------------------------------------------------------------- shard layout

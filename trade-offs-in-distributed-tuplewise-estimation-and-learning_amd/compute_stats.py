@@ -56,8 +56,8 @@ def UB_indices(X, Z, ind_X, ind_Z, kernel):
 
 def UB_pairs(X, Z, indices, kernel):
     """Computes incomplete two-sample U-statistic for given pairs.  (compute_stats.py:32-35)"""
-    idx = np.asarray(list(indices) if not isinstance(indices, (list, np.ndarray)) else indices,
-                     dtype=np.int64).reshape(-1, 2)
+    idx = np.asarray(list(indices) if not isinstance(indices, (list, np.ndarray)) else indices)
+    idx = idx.reshape(-1, 2) if idx.size else idx.astype(np.int64).reshape(-1, 2)
     return UB_indices(X, Z, idx[:, 0], idx[:, 1], kernel)
 
 
@@ -189,7 +189,8 @@ def conv_AUC_deter_pairs(margin, *, loss="hinge"):
 
     def res(X, Z, indices):
         """Computes the convexification of the 1-AUC that we minimize."""
-        idx = np.asarray(indices, dtype=np.int64).reshape(-1, 2)
+        idx = np.asarray(indices)  # its own dtype: _check_index refuses what NumPy refuses
+        idx = idx.reshape(-1, 2) if idx.size else idx.astype(np.int64).reshape(-1, 2)
         X = np.asarray(X)
         Z = np.asarray(Z)
         ix = _check_index(idx[:, 0], X.shape[0])
@@ -220,9 +221,15 @@ def grad_complete_block(w, margin, *, loss="hinge"):
 
 
 def _check_index(ind: np.ndarray, n: int) -> np.ndarray:
+    """NumPy's checks of an integer index array into an axis of n items, as int64 >= 0."""
     ind = np.asarray(ind)
     if ind.dtype == np.bool_:
         raise NotImplementedError("boolean masks are not pair indices")
+    if ind.dtype.kind not in "iu":  # NumPy never truncates a float index
+        raise IndexError("arrays used as indices must be of integer (or boolean) type")
+    if ind.dtype.kind == "u" and ind.size and int(ind.max()) >= 2 ** 63:
+        # NumPy's cast to intp wraps these negative (out of bounds, or silently from the end)
+        raise IndexError(f"index {int(ind.max())} is out of bounds for axis 0 with size {n}")
     ind = ind.astype(np.int64, copy=False)
     if ind.size:
         lo, hi = int(ind.min()), int(ind.max())

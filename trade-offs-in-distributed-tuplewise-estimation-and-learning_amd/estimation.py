@@ -198,11 +198,14 @@ def _replicate_fixed(estimator, gen_X, gen_Z, n_tries, spec, reps, N, sampling_t
 
     def alloc(rows, cols, dtype):
         # page-locked rows on a GPU process (torch's caching host allocator keeps them for
-        # the next call): the flush uploads them by DMA without a packing copy
+        # the next call): the flush uploads them by DMA without a packing copy.  The rows are
+        # native-endian bytes viewed as the samples' dtype (torch has no byte-swapped types;
+        # the row assignments below convert '>f8' samples like any other cast)
+        dtype = np.dtype(dtype).newbyteorder("=")
         if dev is None:
             return np.empty((rows, cols), dtype=dtype)
-        td = t.from_numpy(np.empty(0, dtype=dtype)).dtype
-        return t.empty((rows, cols), dtype=td, pin_memory=True).numpy()
+        raw = t.empty((rows, cols * dtype.itemsize), dtype=t.uint8, pin_memory=True).numpy()
+        return raw.view(dtype)
 
     def work(bx, bz, lay):
         if dev is not None:

@@ -87,10 +87,11 @@ def randint_batch(calls) -> list:
 
 def _shuffle_items(a):
     """(items, item bytes) when np.random.shuffle(a) is the buffer path this module restates:
-    a C-contiguous, non-object ndarray (rows of a 2-D array are items); else None."""
+    a C-contiguous, writeable, non-object ndarray (rows of a 2-D array are items); else None
+    (np.random.shuffle itself raises ValueError for a read-only array)."""
     if not isinstance(a, np.ndarray) or a.ndim == 0 or a.dtype.hasobject:
         return None
-    if not a.flags.c_contiguous or a.size == 0:
+    if not a.flags.c_contiguous or not a.flags.writeable or a.size == 0:
         return None
     return a.shape[0], a.itemsize * (a.size // a.shape[0])
 
