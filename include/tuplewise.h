@@ -199,6 +199,16 @@ int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off, int64_t x_
                          const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                          int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
                          int32_t half, uint64_t* d_out, void* stream);
+/* tw_count_pairs_chain with the caller's promise that every x and z image is an integer in
+ * [0, image_bound] (x images also: the -2^25 "never" image of a NaN score).  With the strict
+ * predicate (half = 0) and image_bound < 2^24 the count runs bit-sliced (k_count_chain_bits,
+ * 32 pairs per lane and instruction); half = 1 or a larger bound runs
+ * tw_count_pairs_chain's packed kernel.  The counts are the same either way. */
+int tw_count_pairs_chain_bound(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
+                               const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
+                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
+                               int32_t half, int64_t image_bound, uint64_t* d_out,
+                               void* stream);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
  * estimation-experiment/main.py:29-31's integer): each bag's z images (integers in
  * [0, z_total], z_total = the Z count the images were ranked against) counting-sorted into
@@ -213,8 +223,10 @@ int tw_count_pairs_chain_bucket(const void* d_x_bag, const int64_t* d_x_off, int
  * round (1 or 16 / elements per thread); 0 = automatic.  Process-global; results do not depend
  * on it (the order inside a bag does). */
 int tw_chain_set_emit(int32_t epr, int32_t steps_per_round);
-/* Tuning hook for tw_count_pairs_chain: x-images per lane (8 or 16; 0 = automatic) and z-chunk
- * length (0 = automatic).  Process-global; results do not depend on it. */
+/* Tuning hook for tw_count_pairs_chain and tw_count_pairs_chain_bound: R = 8 or 16 x-images per
+ * lane forces the packed kernel, R = 2 or 4 plane groups per lane the bit-sliced one (where
+ * the call allows it: a bound below 2^24, strict predicate), 0 = automatic; z-chunk length
+ * for either kernel (0 = automatic).  Process-global; results do not depend on it. */
 int tw_count_chain_set_plan(int32_t R, int64_t z_chunk);
 /* The scores in their final order after the chains (one process): d_x_out[d_x_pos[e]] =
  * d_x[e] (8-B values), likewise for Z. */
@@ -931,6 +943,13 @@ int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int32_t steps, 
                           uint32_t* d_cursors, int32_t* d_flag, const int64_t* d_x_off,
                           const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
                           uint64_t* d_out, void* stream);
+/* tw_chain_unpack_count whose count is tw_count_pairs_chain_bound's (image_bound: its promise). */
+int tw_chain_unpack_count_bound(const uint64_t* d_recv, int32_t world, int32_t steps, int64_t cap,
+                                int32_t half, int64_t n_x, int64_t n_z, int64_t x_shard,
+                                int64_t z_shard, int32_t n_shards, void* d_x_bag, void* d_z_bag,
+                                uint32_t* d_cursors, int32_t* d_flag, const int64_t* d_x_off,
+                                const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
+                                int64_t image_bound, uint64_t* d_out, void* stream);
 /* The incomplete statistic on the step chains over ranks (cs.UnNBT, compute_stats.py:119-123,
  * with device-RNG draws): tw_chain_unpack_exact writes every received record {image, local
  * position} of a chunk's (source, step) buckets (tw_chain_emit's exchange layout, strict

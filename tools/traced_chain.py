@@ -17,8 +17,10 @@ PAIRS_PER_STEP = 64 * 15625 * 15625  # n = 1e6/class, N = 64 shards
 PEAK = 256 * 64 * 2.4e9  # lane-op/s
 
 path, K, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
+# (the strict count: the packed k_count_chain<R, false> or the bit-sliced k_count_chain_bits<NB, R>)
 rows = [r for r in csv.DictReader(open(path))
-        if "k_count_chain<" in r["Kernel_Name"] and ", false>" in r["Kernel_Name"]]
+        if ("k_count_chain<" in r["Kernel_Name"] and ", false>" in r["Kernel_Name"])
+        or "k_count_chain_bits<" in r["Kernel_Name"]]
 grid = lambda r: int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)
 g = max(grid(r) for r in rows)
 big = sorted((r for r in rows if grid(r) == g), key=lambda r: int(r["Start_Timestamp"]))

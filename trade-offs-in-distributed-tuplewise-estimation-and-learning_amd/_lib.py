@@ -55,6 +55,8 @@ _SIGNATURES = {
                         _vp],
     "tw_count_pairs_chain": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32, _vp,
                              _vp],
+    "tw_count_pairs_chain_bound": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32,
+                                   _i64, _vp, _vp],
     "tw_count_pairs_chain_bucket": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64,
                                     _i32, _vp, _vp],
     "tw_count_chain_set_plan": [_i32, _i64],
@@ -207,6 +209,8 @@ _SIGNATURES = {
     "tw_chain_walk": [_i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
     "tw_chain_unpack_count": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp,
                               _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "tw_chain_unpack_count_bound": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
     "tw_chain_unpack_exact": [_vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "tw_count_pairs_chain_rng": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64,
                                  _u64, _u64, _vp, _vp],

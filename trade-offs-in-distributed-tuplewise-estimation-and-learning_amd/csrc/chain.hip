@@ -31,6 +31,7 @@
 // Half ties (tie_mode = "half"): an x image is the pair {g(x), h(x)}, h(x) = #{z : z <= x}
 // (tw_rank_images_query with half = 1), and ONE clamped packed add gives [x > z] and [x >= z]
 // for a z: clamp(h(x) - g(z)) == 1 <=> x >= z.  Half units = the sum of both lanes.
+#include "bitcount.h"
 #include "feistel.h"
 #include "pkcount.h"
 #include "records.h"
@@ -449,13 +450,15 @@ __device__ __forceinline__ unsigned long long count_chain_item(const void* __res
 
 // Work items as k_count_rank (csrc/rankimage.hip): per wave (bag v = step * N + shard, x tile,
 // z chunk), shard-major logical order dealt to the XCDs in contiguous ranges, one u64 atomic
-// per block and bag.
-template <int R, bool HALF>
-__global__ __launch_bounds__(kBlock) void k_count_chain(
-    const void* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
-    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
-    int n_shards, int n_bags, int tiles_x, int zchunks, int64_t z_chunk,
-    unsigned long long* __restrict__ out) {
+// per block and bag.  TILE: x images per item; item(x0, xe, z0, z1, lane) -> the lane's count.
+template <int TILE, class Item>
+__device__ __forceinline__ void count_chain_block(const int64_t* __restrict__ x_off,
+                                                  int64_t x_stride,
+                                                  const int64_t* __restrict__ z_off,
+                                                  int64_t z_stride, int n_shards, int n_bags,
+                                                  int tiles_x, int zchunks, int64_t z_chunk,
+                                                  unsigned long long* __restrict__ out,
+                                                  Item item_count) {
   const int per_bag = tiles_x * zchunks;
   const int lb = xcd_block(blockIdx.x, gridDim.x);
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -472,13 +475,13 @@ __global__ __launch_bounds__(kBlock) void k_count_chain(
     const int64_t xo = (int64_t)c * x_stride, zo = (int64_t)c * z_stride;
     const int64_t xbg = xo + x_off[s], zbg = zo + z_off[s], ze = zo + z_off[s + 1];
     xe = xo + x_off[s + 1];
-    x0 = xbg + (int64_t)tx * (kWave * R);
+    x0 = xbg + (int64_t)tx * TILE;
     z0 = zbg + (int64_t)cz * z_chunk;
     z1 = (z0 + z_chunk < ze) ? z0 + z_chunk : ze;
     active = x0 < xe && z0 < ze;
   }
   unsigned long long tot = 0;
-  if (active) tot = count_chain_item<R, HALF>(xb, x0, xe, zb, z0, z1, lane);
+  if (active) tot = item_count(x0, xe, z0, z1, lane);
   __shared__ unsigned long long part[kBlock / kWave];
   __shared__ int part_v[kBlock / kWave];
   if (lane == 0) {
@@ -500,6 +503,44 @@ __global__ __launch_bounds__(kBlock) void k_count_chain(
     }
     if (cur >= 0 && sum) atomicAdd(out + cur, sum);
   }
+}
+
+template <int R, bool HALF>
+__global__ __launch_bounds__(kBlock) void k_count_chain(
+    const void* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int tiles_x, int zchunks, int64_t z_chunk,
+    unsigned long long* __restrict__ out) {
+  count_chain_block<kWave * R>(
+      x_off, x_stride, z_off, z_stride, n_shards, n_bags, tiles_x, zchunks, z_chunk, out,
+      [&](int64_t x0, int64_t xe, int64_t z0, int64_t z1, int lane) {
+        return count_chain_item<R, HALF>(xb, x0, xe, zb, z0, z1, lane);
+      });
+}
+
+// The bit-sliced count (bitcount.h; strict predicate, images in [0, 2^NB)): an item is
+// 64 * 32 * R x images as R groups of NB bit planes per lane against one z chunk, NB + 1 VALU
+// instructions per 64 * 32 pairs where the packed form takes 32.  Same work items, XCD order,
+// ragged tails (x slots past the bag hold image 0, z slots past the chunk the complemented 0)
+// and epilogue as k_count_chain.
+template <int NB, int R>
+__device__ __forceinline__ unsigned long long count_chain_item_bits(
+    const float* __restrict__ xf, int64_t x0, int64_t xe, const float* __restrict__ zf,
+    int64_t z0, int64_t z1, int lane) {
+  return wave_sum_u64(bits_count_item<NB, R>(xf, x0, xe, zf, z0, z1, lane));
+}
+
+template <int NB, int R>
+__global__ __launch_bounds__(kBlock) void k_count_chain_bits(
+    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int tiles_x, int zchunks, int64_t z_chunk,
+    unsigned long long* __restrict__ out) {
+  count_chain_block<kWave * 32 * R>(
+      x_off, x_stride, z_off, z_stride, n_shards, n_bags, tiles_x, zchunks, z_chunk, out,
+      [&](int64_t x0, int64_t xe, int64_t z0, int64_t z1, int lane) {
+        return count_chain_item_bits<NB, R>(xb, x0, xe, zb, z0, z1, lane);
+      });
 }
 
 // ------------------------------------------- the call's final arrays over ranks: one exchange
@@ -711,6 +752,7 @@ __global__ __launch_bounds__(kBlock) void k_chain_walk(int64_t xbase, int64_t nx
 struct ChainPlan {
   int R, tiles_x, zchunks;
   int64_t z_chunk, blocks;
+  int nb;  // bit planes of k_count_chain_bits; 0: the packed kernel
 };
 static int g_chain_R = 0;  // tuning hooks (tw_count_chain_set_plan); 0 = automatic
 static int64_t g_chain_zchunk = 0;
@@ -726,10 +768,26 @@ constexpr int64_t kChainItems = 256 * 4 * 150;
 // (C2's single 1e5 x 1e5 bag: 600-image chunks 276.9 us, 512 282.3 us, profiles/
 // r05s59_c2_plan.log; the large shapes are indifferent between 512 and 1024)
 constexpr int64_t kChainMinZ = 600;
-static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool half) {
-  ChainPlan p{half ? 8 : 16, 1, 1, max_nz, 0};
+// The bit-sliced kernel (nb > 0: strict predicate and an image bound below 2^24 given): R in
+// {2, 4} plane groups per lane, x tiles of 64 * 32 * R images, least padded slots; on a tie
+// R = 4, or R = 2 where 4 would leave fewer than ~2 items per SIMD (a G = 8 rank's K = 4
+// chunk, 32 bags: 0.190 against 0.206 ms).  An item opens with its bit transposes (~780 VALU
+// instructions per group against R * (nb + 1) + 1 per z), so chunks are longer than the
+// packed kernel's: >= kBitsMinZ images, as many as give ~40 items per SIMD (kBitsItems), of
+// even length.  A bag much smaller than a tile pads more slots than the bit-sliced loop
+// gains (1.39x per slot, profiles/r07_mb_bits.log): past kBitsMaxPad x the packed plan's
+// slots the packed kernel keeps the launch.  tools/count_bits_ab.py, interleaved A/B against
+// the packed kernel (profiles/r07_count_bits_ab.json): headline K = 20 8.48 -> 5.77 ms,
+// K = 32 13.26 -> 9.07, K = 4 1.79 -> 1.19; per-rank shapes G = 2 / 4 / 8 at K = 20 0.66-0.67
+// of the packed time, C2 (one 1e5 x 1e5 bag, R = 2) 0.294 -> 0.260; none slower.
+constexpr int64_t kBitsItems = 256 * 4 * 40;
+constexpr int64_t kBitsMinZ = 1024;
+constexpr double kBitsMaxPad = 1.25;
+static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool half,
+                            int nb) {
+  ChainPlan p{half ? 8 : 16, 1, 1, max_nz, 0, 0};
+  int64_t best = -1;
   if (!half) {
-    int64_t best = -1;
     for (int R : {16, 8}) {
       if (g_chain_R && R != g_chain_R) continue;
       const int64_t slots = ceil_div(max_nx, (int64_t)kWave * R) * kWave * R;
@@ -738,17 +796,41 @@ static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool
         p.R = R;
       }
     }
+    if (nb > 0 && g_chain_R != 8 && g_chain_R != 16) {
+      int64_t bbest = -1;
+      int bR = 0;
+      // on a tie R = 4, unless that leaves fewer than ~2 items per SIMD (R = 2: twice as many)
+      const bool few = ceil_div(max_nx, (int64_t)kWave * 32 * 4) * n_bags *
+                           ceil_div(max_nz, kBitsMinZ) < 256 * 4 * 2;
+      const int tieR = few ? 2 : 4;
+      for (int R : {tieR, 6 - tieR}) {
+        if (g_chain_R && R != g_chain_R) continue;
+        const int64_t slots = ceil_div(max_nx, (int64_t)kWave * 32 * R) * kWave * 32 * R;
+        if (bbest < 0 || slots < bbest) {
+          bbest = slots;
+          bR = R;
+        }
+      }
+      if (g_chain_R || (double)bbest <= kBitsMaxPad * (double)best) {
+        p.R = bR;
+        p.nb = nb;
+      }
+    }
   }
-  p.tiles_x = (int)ceil_div(max_nx, (int64_t)kWave * p.R);
+  const int64_t tile = p.nb ? (int64_t)kWave * 32 * p.R : (int64_t)kWave * p.R;
+  p.tiles_x = (int)ceil_div(max_nx, tile);
   const int64_t base = (int64_t)p.tiles_x * n_bags;
   int64_t zc = g_chain_zchunk;
   if (zc <= 0)
     zc = std::max<int64_t>(
-        kChainMinZ,
-        ceil_div(max_nz, std::max<int64_t>(1, ceil_div(kChainItems, std::max<int64_t>(1, base)))));
+        p.nb ? kBitsMinZ : kChainMinZ,
+        ceil_div(max_nz, std::max<int64_t>(1, ceil_div(p.nb ? kBitsItems : kChainItems,
+                                                       std::max<int64_t>(1, base)))));
   zc = std::min<int64_t>(zc, (int64_t)1 << 24);  // f32 lane counters stay exact
   p.z_chunk = ceil_div(std::min<int64_t>(zc, max_nz), 8) * 8;
   p.zchunks = (int)ceil_div(max_nz, p.z_chunk);
+  if (p.nb && g_chain_zchunk <= 0)  // the same number of chunks, of even length
+    p.z_chunk = ceil_div(ceil_div(max_nz, (int64_t)p.zchunks), 8) * 8;
   p.blocks = ceil_div((int64_t)p.tiles_x * p.zchunks * n_bags, kBlock / kWave);
   return p;
 }
@@ -1003,14 +1085,15 @@ namespace tw {
 static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                               const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
-                              int32_t half, uint64_t* d_out, hipStream_t st);
+                              int32_t half, int64_t image_bound, uint64_t* d_out,
+                              hipStream_t st);
 }  // namespace tw
 
-extern "C" int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off,
-                                    int64_t x_stride, const void* d_z_bag,
-                                    const int64_t* d_z_off, int64_t z_stride, int32_t n_shards,
-                                    int32_t steps, int64_t max_nx, int64_t max_nz, int32_t half,
-                                    uint64_t* d_out, void* stream) {
+static int count_pairs_chain_impl(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
+                                  const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
+                                  int32_t n_shards, int32_t steps, int64_t max_nx,
+                                  int64_t max_nz, int32_t half, int64_t image_bound,
+                                  uint64_t* d_out, void* stream) {
   TW_ARG_CHECK(n_shards >= 0 && steps >= 0 && max_nx >= 0 && max_nz >= 0 && x_stride >= 0 &&
                    z_stride >= 0 && (half == 0 || half == 1),
                "tw_count_pairs_chain: bad sizes");
@@ -1020,7 +1103,32 @@ extern "C" int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off,
   if (bags == 0) return TW_OK;
   TW_HIP_CHECK(tw_zero_async(d_out, 0, sizeof(uint64_t) * (size_t)bags, st));
   return count_chain_launch(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride, n_shards,
-                            steps, max_nx, max_nz, half, d_out, st);
+                            steps, max_nx, max_nz, half, image_bound, d_out, st);
+}
+
+extern "C" int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off,
+                                    int64_t x_stride, const void* d_z_bag,
+                                    const int64_t* d_z_off, int64_t z_stride, int32_t n_shards,
+                                    int32_t steps, int64_t max_nx, int64_t max_nz, int32_t half,
+                                    uint64_t* d_out, void* stream) {
+  return count_pairs_chain_impl(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride,
+                                n_shards, steps, max_nx, max_nz, half, -1, d_out, stream);
+}
+
+// tw_count_pairs_chain with the caller's promise that every x and z image lies in
+// [0, image_bound] (x also: the -2^25 "never" image): the strict predicate with
+// image_bound < 2^24 takes the bit-sliced kernel (k_count_chain_bits), everything else the
+// packed one.  Same counts either way.
+extern "C" int tw_count_pairs_chain_bound(const void* d_x_bag, const int64_t* d_x_off,
+                                          int64_t x_stride, const void* d_z_bag,
+                                          const int64_t* d_z_off, int64_t z_stride,
+                                          int32_t n_shards, int32_t steps, int64_t max_nx,
+                                          int64_t max_nz, int32_t half, int64_t image_bound,
+                                          uint64_t* d_out, void* stream) {
+  TW_ARG_CHECK(image_bound >= 0, "tw_count_pairs_chain_bound: image_bound >= 0");
+  return count_pairs_chain_impl(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride,
+                                n_shards, steps, max_nx, max_nz, half, image_bound, d_out,
+                                stream);
 }
 
 // Over ranks, a chunk's receive side in ONE call: the unpack's cursors and the counts zeroed by
@@ -1040,13 +1148,13 @@ static __global__ __launch_bounds__(256) void k_zero_two(uint32_t* __restrict__ 
   }
 }
 
-extern "C" int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int32_t steps,
-                                     int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
+static int chain_unpack_count_impl(const uint64_t* d_recv, int32_t world, int32_t steps,
+                                   int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
                                      int64_t x_shard, int64_t z_shard, int32_t n_shards,
                                      void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
                                      int32_t* d_flag, const int64_t* d_x_off,
                                      const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
-                                     uint64_t* d_out, void* stream) {
+                                     int64_t image_bound, uint64_t* d_out, void* stream) {
   TW_ARG_CHECK(world >= 1 && steps >= 0 && steps <= kChainMax && cap >= 1 && n_x >= 0 &&
                    n_z >= 0 && (half == 0 || half == 1) && (int64_t)world * steps < 65536 &&
                    x_shard >= 0 && z_shard >= 0 && n_shards >= 0 && n_shards < kEmMaxBig &&
@@ -1072,23 +1180,82 @@ extern "C" int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int3
                      d_x_bag, (uint32_t*)d_z_bag, (unsigned*)d_cursors, d_flag);
   TW_LAUNCH_CHECK();
   return count_chain_launch(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
-                            max_nx, max_nz, half, d_out, st);
+                            max_nx, max_nz, half, image_bound, d_out, st);
+}
+
+extern "C" int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int32_t steps,
+                                     int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
+                                     int64_t x_shard, int64_t z_shard, int32_t n_shards,
+                                     void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
+                                     int32_t* d_flag, const int64_t* d_x_off,
+                                     const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
+                                     uint64_t* d_out, void* stream) {
+  return chain_unpack_count_impl(d_recv, world, steps, cap, half, n_x, n_z, x_shard, z_shard,
+                                 n_shards, d_x_bag, d_z_bag, d_cursors, d_flag, d_x_off, d_z_off,
+                                 max_nx, max_nz, -1, d_out, stream);
+}
+
+// tw_chain_unpack_count with tw_count_pairs_chain_bound's promise for the count
+extern "C" int tw_chain_unpack_count_bound(const uint64_t* d_recv, int32_t world, int32_t steps,
+                                           int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
+                                           int64_t x_shard, int64_t z_shard, int32_t n_shards,
+                                           void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
+                                           int32_t* d_flag, const int64_t* d_x_off,
+                                           const int64_t* d_z_off, int64_t max_nx,
+                                           int64_t max_nz, int64_t image_bound, uint64_t* d_out,
+                                           void* stream) {
+  TW_ARG_CHECK(image_bound >= 0, "tw_chain_unpack_count_bound: image_bound >= 0");
+  return chain_unpack_count_impl(d_recv, world, steps, cap, half, n_x, n_z, x_shard, z_shard,
+                                 n_shards, d_x_bag, d_z_bag, d_cursors, d_flag, d_x_off, d_z_off,
+                                 max_nx, max_nz, image_bound, d_out, stream);
 }
 
 namespace tw {
+template <int NB>
+static void count_chain_launch_bits(const ChainPlan& p, const float* xb, const int64_t* d_x_off,
+                                    int64_t x_stride, const float* zb, const int64_t* d_z_off,
+                                    int64_t z_stride, int n_shards, int bags,
+                                    unsigned long long* o, hipStream_t st) {
+  dim3 g((unsigned)p.blocks), b(kBlock);
+  if (p.R == 4)
+    hipLaunchKernelGGL((k_count_chain_bits<NB, 4>), g, b, 0, st, xb, d_x_off, x_stride, zb,
+                       d_z_off, z_stride, n_shards, bags, p.tiles_x, p.zchunks, p.z_chunk, o);
+  else
+    hipLaunchKernelGGL((k_count_chain_bits<NB, 2>), g, b, 0, st, xb, d_x_off, x_stride, zb,
+                       d_z_off, z_stride, n_shards, bags, p.tiles_x, p.zchunks, p.z_chunk, o);
+}
+
+// image_bound < 0: no bound promised (the packed kernel)
 static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                               const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
-                              int32_t half, uint64_t* d_out, hipStream_t st) {
+                              int32_t half, int64_t image_bound, uint64_t* d_out,
+                              hipStream_t st) {
   const int64_t bags = (int64_t)n_shards * steps;
   if (max_nx == 0 || max_nz == 0) return TW_OK;
-  const ChainPlan p = plan_chain(max_nx, max_nz, bags, half != 0);
+  const ChainPlan p = plan_chain(max_nx, max_nz, bags, half != 0, bits_pick_nb(image_bound));
   TW_ARG_CHECK(p.blocks * (kBlock / kWave) < (1ll << 31) && bags < (1ll << 31),
                "tw_count_pairs_chain: grid too large");
   dim3 g((unsigned)p.blocks), b(kBlock);
   auto* o = (unsigned long long*)d_out;
   const float* zb = (const float*)d_z_bag;
-  if (half)
+  const float* xf = (const float*)d_x_bag;
+  if (p.nb == 16)
+    count_chain_launch_bits<16>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
+                                (int)bags, o, st);
+  else if (p.nb == 18)
+    count_chain_launch_bits<18>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
+                                (int)bags, o, st);
+  else if (p.nb == 20)
+    count_chain_launch_bits<20>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
+                                (int)bags, o, st);
+  else if (p.nb == 22)
+    count_chain_launch_bits<22>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
+                                (int)bags, o, st);
+  else if (p.nb == 24)
+    count_chain_launch_bits<24>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
+                                (int)bags, o, st);
+  else if (half)
     hipLaunchKernelGGL((k_count_chain<8, true>), g, b, 0, st, d_x_bag, d_x_off, x_stride, zb,
                        d_z_off, z_stride, n_shards, (int)bags, p.tiles_x, p.zchunks, p.z_chunk,
                        o);
@@ -1248,7 +1415,8 @@ extern "C" int tw_count_pairs_chain_bucket(const void* d_x_bag, const int64_t* d
 }
 
 extern "C" int tw_count_chain_set_plan(int32_t R, int64_t z_chunk) {
-  TW_ARG_CHECK(R == 0 || R == 8 || R == 16, "tw_count_chain_set_plan: R in {0, 8, 16}");
+  TW_ARG_CHECK(R == 0 || R == 8 || R == 16 || R == 2 || R == 4,
+               "tw_count_chain_set_plan: R in {0, 8, 16} (packed) or {2, 4} (bit-sliced)");
   TW_ARG_CHECK(z_chunk >= 0 && z_chunk <= (1ll << 24), "tw_count_chain_set_plan: bad z_chunk");
   g_chain_R = R;
   g_chain_zchunk = z_chunk;

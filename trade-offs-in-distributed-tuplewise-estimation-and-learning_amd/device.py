@@ -265,6 +265,13 @@ class HipOps:
         """chain_unpack then count_chain in ONE native call (tw_chain_unpack_count): the
         cursors and counts zeroed by one launch, the three launches back to back."""
         cur = self._unpack_cursors(int(steps) * 2 * (int(n_shards) + 1), x_bag.device)
+        bound = self.image_bound
+        if bound is not None and not half:
+            L.call("tw_chain_unpack_count_bound", L.ptr(recv), int(world), int(steps), int(cap),
+                   0, int(n), int(m), int(kx), int(kz), int(n_shards), L.ptr(x_bag),
+                   L.ptr(z_bag), L.ptr(cur), L.ptr(flag), L.ptr(x_off_dev), L.ptr(z_off_dev),
+                   int(max_nx), int(max_nz), int(bound), L.ptr(out), L.stream_handle())
+            return out
         L.call("tw_chain_unpack_count", L.ptr(recv), int(world), int(steps), int(cap),
                int(bool(half)), int(n), int(m), int(kx), int(kz), int(n_shards), L.ptr(x_bag),
                L.ptr(z_bag), L.ptr(cur), L.ptr(flag), L.ptr(x_off_dev), L.ptr(z_off_dev),
@@ -308,6 +315,20 @@ class HipOps:
                L.ptr(out), L.stream_handle())
         return out
 
+    # The caller's promise for the next count_chain / chain_unpack_count: every rank image of
+    # the bags is an integer in [0, image_bound] (x: or the "never" image).  Set around a call
+    # by bounded_images(); None: no promise, the packed kernel.  With a bound and the strict
+    # predicate the counts run bit-sliced (tw_count_pairs_chain_bound).
+    image_bound = None
+
+    @contextlib.contextmanager
+    def bounded_images(self, bound):
+        prev, self.image_bound = self.image_bound, int(bound)
+        try:
+            yield
+        finally:
+            self.image_bound = prev
+
     def _unpack_cursors(self, words, dev):
         # one buffer per HipOps, grown as needed; unpacks on one stream reuse it in order
         c = getattr(self, "_cursors", None)
@@ -318,6 +339,12 @@ class HipOps:
     def count_chain(self, x_bag, x_off_dev, z_bag, z_off_dev, n_shards, steps, x_stride,
                     z_stride, max_nx, max_nz, half, out):
         """Counts of steps x n_shards bags in one launch into out (steps, n_shards)."""
+        bound = self.image_bound
+        if bound is not None and not half:
+            L.call("tw_count_pairs_chain_bound", L.ptr(x_bag), L.ptr(x_off_dev), int(x_stride),
+                   L.ptr(z_bag), L.ptr(z_off_dev), int(z_stride), int(n_shards), int(steps),
+                   int(max_nx), int(max_nz), 0, int(bound), L.ptr(out), L.stream_handle())
+            return out
         L.call("tw_count_pairs_chain", L.ptr(x_bag), L.ptr(x_off_dev), int(x_stride),
                L.ptr(z_bag), L.ptr(z_off_dev), int(z_stride), int(n_shards), int(steps),
                int(max_nx), int(max_nz), int(bool(half)), L.ptr(out), L.stream_handle())
@@ -458,6 +485,12 @@ class HipOps:
 
     def to_dev(self, arr):
         return L.to_device(arr)
+
+
+def _bounded(ops, bound):
+    """ops.bounded_images(bound) where the ops have it (stand-in ops may not)."""
+    f = getattr(ops, "bounded_images", None)
+    return f(bound) if f is not None else contextlib.nullcontext()
 
 
 class _StaleImages(RuntimeError):
@@ -772,8 +805,10 @@ class ShardedSample:
             xi, zi = self.ops.rank_images_query(self.Z, self.X, self.Z, self.dtype, half,
                                                 compact=True)
             out = self.t.empty((1, self.N), dtype=self.t.int64, device=self.X.device)
-            self.ops.count_chain(xi, self.x_off_dev, zi, self.z_off_dev, self.N, 1,
-                                 self.n_loc, self.m_loc, self.max_nx, self.max_nz, half, out)
+            # images are ranks against this Z: at most its count
+            with _bounded(self.ops, int(self.Z.numel())):
+                self.ops.count_chain(xi, self.x_off_dev, zi, self.z_off_dev, self.N, 1,
+                                     self.n_loc, self.m_loc, self.max_nx, self.max_nz, half, out)
             return out[0]
         return self.ops.count(self.X, self.x_off_dev, self.Z, self.z_off_dev, self.N,
                               self.max_nx, self.max_nz, self.dtype, self.pred, algo=self.algo)
@@ -1167,8 +1202,9 @@ class ShardedSample:
                 ops.count_chain_bucket(xb, self.x_off_dev, zb, self.z_off_dev, N, steps, n, m,
                                        self.max_nz, z_total, half, out)
             else:
-                ops.count_chain(xb, self.x_off_dev, zb, self.z_off_dev, N, steps, n, m,
-                                self.max_nx, self.max_nz, half, out)
+                with _bounded(ops, z_total):
+                    ops.count_chain(xb, self.x_off_dev, zb, self.z_off_dev, N, steps, n, m,
+                                    self.max_nx, self.max_nz, half, out)
         x_bag = self._work("x_bag", (C, n), t.int64 if half else t.float32)
         z_bag = self._work("z_bag", (C, m), t.float32)
         xpos = self._work("xpos", (n,), t.int32)
@@ -1233,10 +1269,12 @@ class ShardedSample:
                         work.wait()
                     if rng is None and not bucket and hasattr(ops, "chain_unpack_count"):
                         # the receive side in one native call (unpack + count)
-                        ops.chain_unpack_count(recvs[j], G, cs, cap, half, n, m, x_bag[a:a + cs],
-                                               z_bag[a:a + cs], self._chain_flag, kx, kz, N,
-                                               self.x_off_dev, self.z_off_dev, self.max_nx,
-                                               self.max_nz, counts[i0 + a:i0 + a + cs])
+                        with _bounded(ops, z_total):
+                            ops.chain_unpack_count(recvs[j], G, cs, cap, half, n, m,
+                                                   x_bag[a:a + cs], z_bag[a:a + cs],
+                                                   self._chain_flag, kx, kz, N, self.x_off_dev,
+                                                   self.z_off_dev, self.max_nx, self.max_nz,
+                                                   counts[i0 + a:i0 + a + cs])
                         continue
                     if rng is not None:
                         ops.chain_unpack_exact(recvs[j], G, cs, cap, n, m, x_bag[a:a + cs],
