@@ -233,21 +233,6 @@ int tw_count_chain_set_plan(int32_t R, int64_t z_chunk);
 int tw_chain_scatter(const void* d_x, const uint32_t* d_x_pos, int64_t n_x, const void* d_z,
                      const uint32_t* d_z_pos, int64_t n_z, void* d_x_out, void* d_z_out,
                      void* stream);
-/* The same over ranks: this rank's final positions [x_base, x_base + n_x) of the n_x_all-long
- * X (and Z likewise) walked back through all `steps` repartitions (inverse Feistel, last step
- * first) and gathered from the all-gathered samples d_x_all / d_z_all.  d_work: n_x + n_z u32
- * when steps > 32. */
-int tw_chain_gather(const void* d_x_all, const void* d_z_all, int64_t x_base, int64_t n_x,
-                    int64_t n_x_all, int64_t z_base, int64_t n_z, int64_t n_z_all,
-                    const uint64_t* keys_x, const uint64_t* keys_z, int32_t steps,
-                    uint32_t* d_work, void* d_x_out, void* d_z_out, void* stream);
-/* tw_chain_gather of a second pair of arrays laid out like the first (the carried rank-image
- * records beside the scores) from the same walk of the inverse chains. */
-int tw_chain_gather2(const void* d_x_all, const void* d_z_all, const void* d_x_all2,
-                     const void* d_z_all2, int64_t x_base, int64_t n_x, int64_t n_x_all,
-                     int64_t z_base, int64_t n_z, int64_t n_z_all, const uint64_t* keys_x,
-                     const uint64_t* keys_z, int32_t steps, uint32_t* d_work, void* d_x_out,
-                     void* d_z_out, void* d_x_out2, void* d_z_out2, void* stream);
 
 /* ---- f4: the same counts in O((n+m) log m): sort each z-chunk (<= 16384 keys) in LDS as
  * order-preserving u64 keys, then binary-search every x (csrc/rankcount.hip).  Bit-identical
@@ -916,8 +901,7 @@ int tw_stage_eval(const void* d_res, int32_t nres, const void* d_w, int32_t nw,
  * position} (d_send: world * (cap + 1) * 3 u64; d_cursor: world u64, zero on entry, left
  * zero); after an equal-split all-to-all tw_chain_final_scatter writes every received record
  * at its position of d_x_out / d_x_rec_out / d_z_out / d_z_rec_out (n_x / n_z 8-B words).
- * Replaces est.UnNT's final in-place arrays (main.py:46-47) gathered by inverse chains from
- * all-gathered samples.  Overflows raise *d_flag. */
+ * est.UnNT's final in-place arrays (main.py:46-47) over ranks.  Overflows raise *d_flag. */
 int tw_chain_final_pack(const void* d_x, const uint64_t* d_x_rec, const uint32_t* d_x_pos,
                         int64_t n_x, const void* d_z, const uint64_t* d_z_rec,
                         const uint32_t* d_z_pos, int64_t n_z, int32_t world, int64_t cap,
@@ -925,14 +909,6 @@ int tw_chain_final_pack(const void* d_x, const uint64_t* d_x_rec, const uint32_t
 int tw_chain_final_scatter(const void* d_recv, int32_t world, int64_t cap, int64_t n_x,
                            int64_t n_z, void* d_x_out, void* d_x_rec_out, void* d_z_out,
                            void* d_z_rec_out, int32_t* d_flag, void* stream);
-/* The final global positions of this rank's elements (x: x_base + e, z: z_base + e) after
- * `steps` chained permutations of the n_x_all / n_z_all domains (keys as tw_chain_emit's): the
- * chain state tw_chain_emit leaves after the same steps, computed without emitting, so that
- * tw_chain_final_pack can run at a call's start beside its emissions and counts (main.py:46-47's
- * final arrays, est.UnNT). */
-int tw_chain_walk(int64_t x_base, int64_t n_x, int64_t n_x_all, int64_t z_base, int64_t n_z,
-                  int64_t n_z_all, const uint64_t* keys_x, const uint64_t* keys_z, int32_t steps,
-                  uint32_t* d_x_pos, uint32_t* d_z_pos, void* stream);
 /* A chunk's receive side over ranks in ONE call (round 6): tw_chain_unpack (its arguments, in
  * order) then tw_count_pairs_chain on the filled bags (shard offsets d_x_off / d_z_off, largest
  * shards max_nx / max_nz, bag strides n_x / n_z, out [steps][n_shards]), the cursors and the

@@ -169,7 +169,8 @@ class OracleOpsRank(OracleOpsFixed):
 
 class OracleOpsChain(OracleOpsRank):
     """Adds the step chains (tw_rank_images_query / tw_chain_emit / tw_chain_unpack /
-    tw_count_pairs_chain / tw_chain_scatter / tw_chain_gather, csrc/chain.hip) restated, so
+    tw_count_pairs_chain / tw_chain_scatter / tw_chain_final_pack / tw_chain_final_scatter,
+    csrc/chain.hip) restated, so
     UnN_many takes the chain path on host tensors (bags written at exact positions, one valid
     arrangement of the device's shard multisets)."""
 
@@ -265,15 +266,6 @@ class OracleOpsChain(OracleOpsRank):
         Zo.numpy()[zpos.numpy().view(np.uint32)] = Z.numpy()
         return Xo, Zo
 
-    def chain_walk(self, x_base, n, NX, z_base, m, NZ, keys_x, keys_z, xpos, zpos):
-        """tw_chain_walk restated: the rank's positions through every step, no emission."""
-        for base, cnt, N_, keys, out in ((x_base, n, NX, keys_x, xpos),
-                                         (z_base, m, NZ, keys_z, zpos)):
-            p = np.arange(base, base + cnt)
-            for key in keys:
-                p = O.feistel_perm(p, N_, int(key))
-            out.numpy()[:] = p.astype(np.uint32).view(np.int32)
-
     def chain_final_pack(self, X, xr, xpos, Z, zr, zpos, world, cap, cursor, send, flag):
         """tw_chain_final_pack restated: {score, record, local position} records of the walked
         elements into the buckets of the ranks holding their final positions (a header record
@@ -357,20 +349,6 @@ class OracleOpsChain(OracleOpsRank):
             verdict[0] = good if int(acc[0]) == int(expect[0]) else bad
         return acc
 
-    def chain_gather(self, X_all, Z_all, x_base, n, z_base, m, keys_x, keys_z, X2=None,
-                     Z2=None):
-        out, src = [], []
-        for A, base, cnt, keys in ((X_all, x_base, n, keys_x), (Z_all, z_base, m, keys_z)):
-            p = np.arange(base, base + cnt)
-            for key in reversed(keys):
-                p = O.feistel_perm_inv(p, A.numel(), int(key))
-            out.append(torch.from_numpy(A.numpy()[p].copy()))
-            src.append(p)
-        if X2 is not None:  # tw_chain_gather2: the second pair from the same walk
-            out += [torch.from_numpy(X2.numpy()[src[0]].copy()),
-                    torch.from_numpy(Z2.numpy()[src[1]].copy())]
-        return tuple(out)
-
 
 _OPS = {"plain": OracleOps, "fused": OracleOpsFused, "fixed": OracleOpsFixed,
         "rank": OracleOpsRank, "chain": OracleOpsChain}
@@ -442,17 +420,10 @@ def test_multirank_repartition_is_G_invariant(G, fused):
     assert inc == float(S1.UnNB(B, seed=77))
 
 
-def _rank_worker(rank, G, port, n_loc, m_loc, N, keys, q, tie_mode="strict", sub=0,
-                 final="exchange"):
+def _rank_worker(rank, G, port, n_loc, m_loc, N, keys, q, tie_mode="strict"):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=G)
-    from tuplewise import device as D
     from tuplewise.device import ShardedSample
-    D.CHAIN_SUB = sub
-    # the final arrays: one exchange after the last emission (default), one exchange forked at
-    # the call's start on walked positions (tw_chain_walk), or the inverse-chain gathers
-    D.FINAL_EXCHANGE = final != "gather"
-    D.FINAL_EARLY = final == "early"
     X, Z = _global_data(G, n_loc, m_loc)
     S = ShardedSample(torch.from_numpy(X[rank * n_loc:(rank + 1) * n_loc].copy()),
                       torch.from_numpy(Z[rank * m_loc:(rank + 1) * m_loc].copy()), N,
@@ -470,29 +441,26 @@ def _rank_worker(rank, G, port, n_loc, m_loc, N, keys, q, tie_mode="strict", sub
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("G,tie_mode,sub,final", [
-    (2, "strict", 0, "exchange"), (4, "strict", 0, "exchange"), (8, "strict", 0, "exchange"),
-    (2, "half", 0, "exchange"), (4, "strict", 5, "exchange"), (3, "half", 0, "early"),
-    (2, "strict", 5, "early"), (3, "strict", 0, "gather")])
-def test_chain_steps_are_G_invariant(G, tie_mode, sub, final):
+@pytest.mark.parametrize("G,tie_mode", [
+    (2, "strict"), (4, "strict"), (8, "strict"), (2, "half"), (3, "half"), (3, "strict")])
+def test_chain_steps_are_G_invariant(G, tie_mode):
     """UnN_many's step chains over G ranks (csrc/chain.hip, restated): every rank images its
     own elements against the all-gathered Z, walks their chains into per-(rank, step) buckets,
-    one all-to-all per chunk (sub > 0: per sub-chunk of <= sub steps, async), counts its bags;
-    one all-reduce of the counts per call.  The estimates equal the one-process score path's (est.UnNT's loop, key by key) and the ranks'
-    final arrays, concatenated, equal the global permutation chain."""
+    one all-to-all per chunk, counts its bags; one all-reduce of the counts per call; the final
+    arrays by one exchange of the walked elements.  The estimates equal the one-process score
+    path's (est.UnNT's loop, key by key) and the ranks' final arrays, concatenated, equal the
+    global permutation chain."""
     import tuplewise  # noqa: F401
     from tuplewise import device as D
     assert D.CHAIN_STEPS
     from tuplewise.device import ShardedSample
-    # 12 steps: with sub = 5, sub-chunks of (5, 5, 2) steps, each its own async all-to-all,
-    # unpacked and counted in order
     n_loc, m_loc, N = 600, 450, 3
     keys = [5, 6, 9, 11, 2, 7, 8, 13, 21, 3, 4, 17] if G != 8 else [5, 6, 9, 11, 2, 7, 8]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_rank_worker,
-                         args=(r, G, port, n_loc, m_loc, N, keys, q, tie_mode, sub, final))
+                         args=(r, G, port, n_loc, m_loc, N, keys, q, tie_mode))
              for r in range(G)]
     for p in procs:
         p.start()
@@ -566,6 +534,51 @@ def test_incomplete_chain_steps_are_G_invariant(G):
             for i, keys in enumerate(calls)]
     assert vals == want
     assert np.array_equal(Xg, S1.X.numpy()) and np.array_equal(Zg, S1.Z.numpy())
+
+
+class OracleOpsNoRanking(OracleOpsChain):
+    """The step chains' operations with a ranking that declines (tw_rank_images_query's None)."""
+
+    def rank_images_query(self, Z_all, X, Z, dtype, half=False):
+        return None
+
+
+def _no_ranking_worker(port, B, seed, keys, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    from tuplewise.device import ShardedSample
+    X, Z = _global_data(1, 1800, 1350)
+    S = ShardedSample(torch.from_numpy(X.copy()), torch.from_numpy(Z.copy()), 9,
+                      group=dist.group.WORLD, ops=OracleOpsNoRanking(), algo="pairs",
+                      collectives=True)
+    assert S.coll and S._chain_rng_ok()  # UnNB_many enters _chain_call with rng
+    inc = [float(v) for v in S.UnNB_many(B, seed, keys)]
+    q.put((inc, S.X.numpy().copy(), S.Z.numpy().copy()))
+    dist.destroy_process_group()
+
+
+def test_chain_call_without_ranking_keeps_the_incomplete_statistic():
+    """when the ranking declines, _chain_call falls back to the per-step path —
+    for UnNB_many (rng = (B, seed)) that is UnNB(B, seed + t, key_t), the incomplete statistic
+    with its draws, not the complete UnN(key_t)."""
+    import tuplewise  # noqa: F401
+    from tuplewise.device import ShardedSample
+    B, seed, keys = 700, 0xC3C3_0042, [5, 6, 9, 11]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_no_ranking_worker, args=(_free_port(), B, seed, keys, q))
+    p.start()
+    inc, Xf, Zf = q.get(timeout=240)
+    p.join(timeout=60)
+    assert p.exitcode == 0
+    X, Z = _global_data(1, 1800, 1350)
+    S1 = ShardedSample(torch.from_numpy(X.copy()), torch.from_numpy(Z.copy()), 9,
+                       ops=OracleOps(), algo="pairs")
+    assert inc == [float(S1.UnNB(B, seed + t, k)) for t, k in enumerate(keys)]  # the score path
+    assert np.array_equal(Xf, S1.X.numpy()) and np.array_equal(Zf, S1.Z.numpy())
+    S2 = ShardedSample(torch.from_numpy(X.copy()), torch.from_numpy(Z.copy()), 9,
+                       ops=OracleOps(), algo="pairs")
+    assert inc != [float(S2.UnN(k)) for k in keys]  # (the complete values differ here)
 
 
 def _overflow_worker(rank, G, port, q):
@@ -677,7 +690,7 @@ def _forced_worker(port, q):
 def test_forced_collectives_at_world_size_one_equal_one_process():
     """VERDICT r04 item 1 on CPU: ShardedSample(collectives=True) on a world-size-1 group runs
     the multi-rank branches (all-gathers, chain emission into send buckets, the all-to-all,
-    unpack, chain_gather, the counts' all-reduce, the fixed exchange) and must equal the
+    unpack, the final exchange, the counts' all-reduce, the fixed exchange) and must equal the
     one-process path bit for bit; tests/test_gpu_rccl.py runs the same on RCCL."""
     import tuplewise  # noqa: F401
     from tuplewise.device import ShardedSample
@@ -738,8 +751,8 @@ def _carry_worker(rank, G, port, q, mode):
                                     (2, "hidden"), (3, "hidden_one")])
 def test_carried_images_over_ranks(G, mode):
     """device.CARRY_IMAGES over ranks: the second and later UnN_many calls carry every rank's
-    records through the inverse chains (all-gathered records, chain_gather) instead of ranking
-    again; estimates and final arrays equal the one-process score path call after call.  An
+    records with their elements through the final exchange (chain_final_pack / _scatter) instead
+    of ranking again; estimates and final arrays equal the one-process score path call after call.  An
     in-place change of the sample on every rank drops the carried images; on one rank alone the
     ranks disagree and every rank recounts the call from a fresh ranking.  A write behind the
     version counter (.data) on every rank or on one is caught by the arrays' checksum

@@ -121,7 +121,9 @@ def test_chain_exchange_simulated_ranks(gpu, G, half):
     (tw_rank_images_query), walks its chains into send buckets (tw_chain_emit, world = G), the
     all-to-all is done by hand (rank r receives every source's chunk for r), tw_chain_unpack
     fills its bags, tw_count_pairs_chain counts them; the ranks' counts equal one process on the
-    global layout of G*N shards, and tw_chain_gather's final arrays equal the oracle chain."""
+    global layout of G*N shards.  The emission's chain state equals the oracle's Feistel
+    positions, and the final exchange on it (tw_chain_final_pack, the all-to-all by hand,
+    tw_chain_final_scatter) gives the oracle chain's final arrays and records."""
     import torch
     from tuplewise import _lib as L
     from tuplewise.device import HipOps
@@ -139,7 +141,7 @@ def test_chain_exchange_simulated_ranks(gpu, G, half):
     tot = n_loc + m_loc
     cap = tot // G + tot // (8 * G) + 1024
     W = 2 if half else 1
-    sends = []
+    sends, walked = [], []
     for r in range(G):
         xq = Xall[r * n_loc:(r + 1) * n_loc]
         zq = Zall[r * m_loc:(r + 1) * m_loc]
@@ -154,12 +156,14 @@ def test_chain_exchange_simulated_ranks(gpu, G, half):
         ops.chain_emit(xr, zr, half, xpos, zpos, True, r, G, kxs, kzs, kx, kz, N, send=send,
                        cap=cap, flag=flag)
         assert int(flag.item()) == 0
-        # tw_chain_walk: the same chain state without emitting
-        wxp, wzp = torch.empty_like(xpos), torch.empty_like(zpos)
-        ops.chain_walk(r * n_loc, n_loc, G * n_loc, r * m_loc, m_loc, G * m_loc, kxs, kzs, wxp,
-                       wzp)
-        assert torch.equal(wxp, xpos) and torch.equal(wzp, zpos)
+        # the chain state: the oracle's Feistel positions of the rank's elements
+        for got, base, nl, ks in ((xpos, r * n_loc, n_loc, kxs), (zpos, r * m_loc, m_loc, kzs)):
+            p = np.arange(base, base + nl)
+            for k in ks:
+                p = O.feistel_perm(p, G * nl, int(k))
+            assert np.array_equal(got.cpu().numpy().view(np.uint32), p)
         sends.append(send.view(G, -1))
+        walked.append((xq, xr, xpos, zq, zr, zpos, wx, wz))
     x_off, z_off = _layout(n_loc, m_loc, N)
     xo, zo = torch.from_numpy(x_off).cuda(), torch.from_numpy(z_off).cuda()
     counts = []
@@ -205,12 +209,45 @@ def test_chain_exchange_simulated_ranks(gpu, G, half):
             same_regions(z_bag[c].cpu().numpy().view(np.uint32),
                          (ez.view(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32), z_off,
                          m_loc)
-        Xo, Zo = ops.chain_gather(Xall, Zall, r * n_loc, n_loc, r * m_loc, m_loc, kxs, kzs)
-        xs, zs = _chain(X, keys, 0), _chain(Z, keys, 1)
-        assert np.array_equal(Xo.cpu().numpy(), xs[-1][r * n_loc:(r + 1) * n_loc])
-        assert np.array_equal(Zo.cpu().numpy(), zs[-1][r * m_loc:(r + 1) * m_loc])
-    got = np.concatenate(counts, axis=1).view(np.uint64)
+    # the final exchange: every rank packs its walked elements by their final positions, the
+    # all-to-all by hand, every rank scatters what it received
+    fcap = tot // G + tot // (8 * G) + 1024
+    fflag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    fsends = []
+    for xq, xr, xpos, zq, zr, zpos, _, _ in walked:
+        fsend = torch.empty(G * (fcap + 1) * 3, dtype=torch.int64, device="cuda")
+        cursor = torch.zeros(G, dtype=torch.int64, device="cuda")
+        ops.chain_final_pack(xq, xr, xpos, zq, zr, zpos, G, fcap, cursor, fsend, fflag)
+        assert int(cursor.abs().sum().item()) == 0  # (left zero for the next call)
+        fsends.append(fsend.view(G, -1))
     xs, zs = _chain(X, keys, 0), _chain(Z, keys, 1)
+    # the records of the whole sample through the chain: their images (and h for half ties) are
+    # the ranks'; the other high words are indices, rank-local in the ranks' records, so the
+    # full words are checked against the ranks' own oracle records through the same chain
+    ax, az = O.rank_records(X, Z, half=half)
+    axf, azf = _chain(ax, keys, 0)[-1], _chain(az, keys, 1)[-1]
+    rxf = _chain(np.concatenate([w[6] for w in walked]), keys, 0)[-1]
+    rzf = _chain(np.concatenate([w[7] for w in walked]), keys, 1)[-1]
+    low = np.uint64(0xFFFFFFFF)
+    for r in range(G):
+        frecv = torch.cat([fsends[g][r] for g in range(G)])
+        xq, xr, _, zq, zr, _, _, _ = walked[r]
+        Xo, Zo = torch.empty_like(xq), torch.empty_like(zq)
+        XRo, ZRo = torch.empty_like(xr), torch.empty_like(zr)
+        ops.chain_final_scatter(frecv, G, fcap, n_loc, m_loc, Xo, XRo, Zo, ZRo, fflag)
+        assert int(fflag.item()) == 0
+        a, b = slice(r * n_loc, (r + 1) * n_loc), slice(r * m_loc, (r + 1) * m_loc)
+        assert np.array_equal(Xo.cpu().numpy(), xs[-1][a])
+        assert np.array_equal(Zo.cpu().numpy(), zs[-1][b])
+        gxr, gzr = XRo.cpu().numpy().view(np.uint64), ZRo.cpu().numpy().view(np.uint64)
+        assert np.array_equal(gxr, rxf[a].view(np.uint64))
+        assert np.array_equal(gzr, rzf[b].view(np.uint64))
+        if half:
+            assert np.array_equal(gxr, axf[a].view(np.uint64))
+        else:
+            assert np.array_equal(gxr & low, axf[a].view(np.uint64) & low)
+        assert np.array_equal(gzr & low, azf[b].view(np.uint64) & low)
+    got = np.concatenate(counts, axis=1).view(np.uint64)
     for c in range(T):
         for g in range(G):
             for s in range(N):
@@ -221,46 +258,42 @@ def test_chain_exchange_simulated_ranks(gpu, G, half):
                 assert int(got[c, g * N + s]) == want
 
 
-def test_chain_gather_many_steps(gpu):
-    """tw_chain_gather over more than 32 steps (chunks walked back through its work array)."""
+def test_chain_state_carried_over_chunks(gpu):
+    """A call of more than 32 steps: the chain state carried over tw_chain_emit calls of 32, 32
+    and 6 steps (`first` only on the first) equals the oracle's Feistel positions of the rank's
+    elements after 32, 64 and 70 steps."""
     import torch
+    from tuplewise import _lib as L
     from tuplewise.device import HipOps
     rng = np.random.RandomState(4)
-    G, n_loc, m_loc = 2, 1000, 700
+    G, n_loc, m_loc, N = 3, 1000, 700, 4
     X, Z = rng.normal(size=G * n_loc), rng.normal(size=G * m_loc)
-    keys = list(range(100, 170))
-    kxs = [(2 * k) & M64 for k in keys]
-    kzs = [(2 * k + 1) & M64 for k in keys]
-    xs, zs = _chain(X, keys, 0)[-1], _chain(Z, keys, 1)[-1]
-    ops = HipOps()
-    for r in range(G):
-        Xo, Zo = ops.chain_gather(torch.from_numpy(X).cuda(), torch.from_numpy(Z).cuda(),
-                                  r * n_loc, n_loc, r * m_loc, m_loc, kxs, kzs)
-        assert np.array_equal(Xo.cpu().numpy(), xs[r * n_loc:(r + 1) * n_loc])
-        assert np.array_equal(Zo.cpu().numpy(), zs[r * m_loc:(r + 1) * m_loc])
-
-
-def test_chain_walk_many_steps(gpu):
-    """tw_chain_walk over more than 32 steps (launch chunks) and over none: the oracle's
-    Feistel positions of the rank's elements."""
-    import torch
-    from tuplewise.device import HipOps
-    G, n_loc, m_loc = 3, 1000, 700
     keys = list(range(300, 370))
     kxs = [(2 * k) & M64 for k in keys]
     kzs = [(2 * k + 1) & M64 for k in keys]
+    kx, kz = int(n_loc / N), int((n_loc + m_loc) / N) - int(n_loc / N)
+    tot = n_loc + m_loc
+    cap = tot // G + tot // (8 * G) + 1024
     ops = HipOps()
+    Zall = torch.from_numpy(Z).cuda()
     for r in range(G):
-        for T in (0, 1, 32, 33, 70):
-            xp = torch.empty(n_loc, dtype=torch.int32, device="cuda")
-            zp = torch.empty(m_loc, dtype=torch.int32, device="cuda")
-            ops.chain_walk(r * n_loc, n_loc, G * n_loc, r * m_loc, m_loc, G * m_loc, kxs[:T],
-                           kzs[:T], xp, zp)
-            for got, base, nl, ks in ((xp, r * n_loc, n_loc, kxs), (zp, r * m_loc, m_loc, kzs)):
-                p = np.arange(base, base + nl)
-                for k in ks[:T]:
-                    p = O.feistel_perm(p, G * nl, int(k))
-                assert np.array_equal(got.cpu().numpy().view(np.uint32), p)
+        xq = torch.from_numpy(X[r * n_loc:(r + 1) * n_loc]).cuda()
+        zq = Zall[r * m_loc:(r + 1) * m_loc]
+        xr, zr = ops.rank_images_query(Zall, xq, zq, L.TW_F64, False)
+        xpos = torch.empty(n_loc, dtype=torch.int32, device="cuda")
+        zpos = torch.empty(m_loc, dtype=torch.int32, device="cuda")
+        send = torch.empty(G * 32 * (cap + 1), dtype=torch.int64, device="cuda")
+        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        px, pz = np.arange(r * n_loc, (r + 1) * n_loc), np.arange(r * m_loc, (r + 1) * m_loc)
+        for t0, t1 in ((0, 32), (32, 64), (64, 70)):
+            ops.chain_emit(xr, zr, False, xpos, zpos, t0 == 0, r, G, kxs[t0:t1], kzs[t0:t1], kx,
+                           kz, N, send=send, cap=cap, flag=flag)
+            for t in range(t0, t1):
+                px = O.feistel_perm(px, G * n_loc, int(kxs[t]))
+                pz = O.feistel_perm(pz, G * m_loc, int(kzs[t]))
+            assert np.array_equal(xpos.cpu().numpy().view(np.uint32), px)
+            assert np.array_equal(zpos.cpu().numpy().view(np.uint32), pz)
+        assert int(flag.item()) == 0
 
 
 @pytest.mark.parametrize("case", ["gauss", "ties_i64", "edge_ragged", "one_shard", "long"])

@@ -77,7 +77,7 @@ XR, ZR = HipOps().rank_images_query(Z, X, Z, L.TW_F64)
 
 def rank_call(G, r, K, parts=False, carried=False):
     """Rank r's device work in one call of the strong problem split over G ranks, the
-    product's schedule (device.CHAIN_SUB = 0: one exchange, unpack and count per chunk).
+    product's schedule (one exchange, unpack and count per chunk).
     carried: a later call of the sample (device.CARRY_IMAGES): no Z all-gather to wait for and
     no ranking; the all-gathers (device copies) and the final gathers of scores and records on
     a side stream."""
@@ -121,10 +121,10 @@ def rank_call(G, r, K, parts=False, carried=False):
     fs = torch.cuda.Stream()
     xr_c, zr_c = XR[r * nl:(r + 1) * nl], ZR[r * nl:(r + 1) * nl]
 
-    # round 6 (device.FINAL_EXCHANGE): the final arrays and carried records by one exchange of
-    # the walked elements, forked on the side stream once the last emission has run
-    # (device.FINAL_EARLY, the fork at the call's start on tw_chain_walk positions, measured
-    # slower: profiles/r06s22_*)
+    # the final arrays and carried records by one exchange of the walked elements
+    # (device._final_exchange), forked on the side stream once the last emission has run (a
+    # fork at the call's start on separately walked positions measured slower and was removed:
+    # profiles/r06s22_*)
     tot = 2 * nl
     fcap = max(1, tot // G + tot // (8 * G) + 1024)
     fsend = torch.empty(G * (fcap + 1) * 3, dtype=torch.int64, device="cuda")

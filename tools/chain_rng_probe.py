@@ -134,10 +134,10 @@ def chain_call(G, r, T, carried, parts=False):
         t.setdefault(name, []).append((e0, e1))
         return out
 
-    # round 6 (device.FINAL_EXCHANGE): the final arrays and carried records by one exchange
-    # of the walked elements, forked on the side stream once the last emission has run
-    # (device.FINAL_EARLY, the fork at the call's start on tw_chain_walk positions, measured
-    # slower: profiles/r06s22_*)
+    # the final arrays and carried records by one exchange of the walked elements
+    # (device._final_exchange), forked on the side stream once the last emission has run (a
+    # fork at the call's start on separately walked positions measured slower and was removed:
+    # profiles/r06s22_*)
     fcap = max(1, tot // G + tot // (8 * G) + 1024)
     fsend = torch.empty(G * (fcap + 1) * 3, dtype=torch.int64, device="cuda")
     frecv = torch.empty_like(fsend)

@@ -62,10 +62,6 @@ _SIGNATURES = {
     "tw_count_chain_set_plan": [_i32, _i64],
     "tw_chain_set_emit": [_i32, _i32],
     "tw_chain_scatter": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp],
-    "tw_chain_gather": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp,
-                        _vp, _vp],
-    "tw_chain_gather2": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32,
-                         _vp, _vp, _vp, _vp, _vp, _vp],
     "tw_count_pairs_sorted_work_bytes": [_i32, _i64],
     "tw_count_sorted_set_chunk": [_i64],
     "tw_count_pairs_sorted": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
@@ -206,7 +202,6 @@ _SIGNATURES = {
     "tw_chain_final_pack": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp,
                             _vp],
     "tw_chain_final_scatter": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
-    "tw_chain_walk": [_i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
     "tw_chain_unpack_count": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp,
                               _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "tw_chain_unpack_count_bound": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32,

@@ -41,29 +41,12 @@ CHAIN_MAX = 32
 # O(n + m) on their integer rank images (tw_count_pairs_chain_bucket); larger shards keep the
 # records path (tw_count_pairs_sorted_steps)
 CHAIN_BUCKET_MAX = 16384
-# several ranks: 0 (default) — one all-to-all per chunk, its unpack and ONE count launch
-# behind it; n > 0 — the chunk's steps in sub-chunks of at most n steps (and at least two),
-# each its own async all-to-all with its emission on a side stream, so one sub-chunk's exchange
-# runs under the previous sub-chunk's count.  Round 5 (tools/chain_probe.py,
-# profiles/r05s36_chain_probe.log): the sub-chunks' extra launches (emission, unpack, count
-# tail, cross-stream waits) cost a G = 8 rank 0.05-0.09 ms per call at T = 4 and 0.13-0.15 ms
-# at T = 20 — more than the exchange they hide (~0.03 / ~0.08 ms over xGMI)
-CHAIN_SUB = 0
 # UnN_many on the step chains carries the rank-image records of the final arrays to the next
 # call: a repartition permutes the sample and never changes its multiset, so the images (ranks
 # against the whole Z) stay valid while the arrays are the ones the chains left — the next call
 # skips the ranking (and over ranks the Z all-gather it waits for).  Any assignment of X / Z or
 # an in-place change (the tensors' version counters) drops them.
 CARRY_IMAGES = True
-# over ranks, a chain call's final arrays and carried records by ONE exchange of the walked
-# elements to the owners of their final positions (tw_chain_final_pack / _scatter), instead of
-# all-gathers of both samples and both record arrays and inverse-chain gathers from them
-FINAL_EXCHANGE = True
-# ... forked at the call's start on positions walked without emitting (tw_chain_walk) instead
-# of after the last emission: off — on one GPU the walk and pack beside the emissions cost more
-# than they hide (profiles/r06s22_chain_probe.log), and over RCCL the exchange's all-to-all
-# issued first would queue ahead of the chunks' on the communicator
-FINAL_EARLY = False
 # one process: the call's final scatters (scores and carried records, memory-bound) on a side
 # stream beside the last chunk's count (VALU-bound) instead of after it — when that count is
 # short (<= FINAL_BESIDE_MAX_STEPS steps): its blocks, starved beside a long count, hold wave
@@ -284,15 +267,6 @@ class HipOps:
                L.ptr(zr), L.ptr(zpos), int(Z.numel()), int(world), int(cap), L.ptr(cursor),
                L.ptr(send), L.ptr(flag), L.stream_handle())
 
-    def chain_walk(self, x_base, n, NX, z_base, m, NZ, keys_x, keys_z, xpos, zpos):
-        """The final positions of the rank's elements after the keys' steps, without emitting
-        (tw_chain_walk): the chain state tw_chain_emit leaves after the same steps."""
-        kxa = np.ascontiguousarray(keys_x, dtype=np.uint64)
-        kza = np.ascontiguousarray(keys_z, dtype=np.uint64)
-        L.call("tw_chain_walk", int(x_base), int(n), int(NX), int(z_base), int(m), int(NZ),
-               kxa.ctypes.data, kza.ctypes.data, len(kxa), L.ptr(xpos), L.ptr(zpos),
-               L.stream_handle())
-
     def chain_final_scatter(self, recv, world, cap, n, m, Xo, XRo, Zo, ZRo, flag):
         """The received final records at their positions (tw_chain_final_scatter)."""
         L.call("tw_chain_final_scatter", L.ptr(recv), int(world), int(cap), int(n), int(m),
@@ -364,31 +338,6 @@ class HipOps:
         L.call("tw_chain_scatter", L.ptr(X), L.ptr(xpos), int(X.numel()), L.ptr(Z),
                L.ptr(zpos), int(Z.numel()), L.ptr(Xo), L.ptr(Zo), L.stream_handle())
         return Xo, Zo
-
-    def chain_gather(self, X_all, Z_all, x_base, n, z_base, m, keys_x, keys_z, X2=None,
-                     Z2=None):
-        """The rank's final arrays: the inverse chains of its own positions, gathered from the
-        all-gathered samples (tw_chain_gather); with X2 / Z2 (laid out like X_all / Z_all:
-        the carried records) also theirs, from the same walk (tw_chain_gather2)."""
-        kxa = np.ascontiguousarray(keys_x, dtype=np.uint64)
-        kza = np.ascontiguousarray(keys_z, dtype=np.uint64)
-        dev = X_all.device
-        Xo = self.t.empty((n,), dtype=X_all.dtype, device=dev)
-        Zo = self.t.empty((m,), dtype=Z_all.dtype, device=dev)
-        work = self.t.empty((max(1, n + m),), dtype=self.t.int32, device=dev)
-        if X2 is None:
-            L.call("tw_chain_gather", L.ptr(X_all), L.ptr(Z_all), int(x_base), int(n),
-                   int(X_all.numel()), int(z_base), int(m), int(Z_all.numel()), kxa.ctypes.data,
-                   kza.ctypes.data, len(kxa), L.ptr(work), L.ptr(Xo), L.ptr(Zo),
-                   L.stream_handle())
-            return Xo, Zo
-        X2o = self.t.empty((n,), dtype=X2.dtype, device=dev)
-        Z2o = self.t.empty((m,), dtype=Z2.dtype, device=dev)
-        L.call("tw_chain_gather2", L.ptr(X_all), L.ptr(Z_all), L.ptr(X2), L.ptr(Z2), int(x_base),
-               int(n), int(X_all.numel()), int(z_base), int(m), int(Z_all.numel()),
-               kxa.ctypes.data, kza.ctypes.data, len(kxa), L.ptr(work), L.ptr(Xo), L.ptr(Zo),
-               L.ptr(X2o), L.ptr(Z2o), L.stream_handle())
-        return Xo, Zo, X2o, Z2o
 
     def count_rng(self, x, x_off_dev, z, z_off_dev, n_shards, B, seed, shard_base, dtype, pred,
                   max_nx=None, max_nz=None):
@@ -1085,21 +1034,33 @@ class ShardedSample:
         image lands in the (step, shard) bag holding its position — directly in one process,
         through ONE equal-split all-to-all of {image, position} records over ranks — and one
         launch counts all bags of the chunk.  The final arrays: a scatter by the chains' last
-        positions (one process) or the inverse chains of the rank's own positions gathered from
-        the all-gathered sample.  Same permutation chain, counts and final arrays as the
-        one-launch-per-step paths, at any G.  bucket: the bags counted exactly in O(n + m) on
-        their integer images (algo="sorted") instead of all pairs — the same integers.
+        positions (one process), or over ranks ONE exchange of the walked elements to the ranks
+        holding their final positions (_final_exchange).  Same permutation chain, counts and
+        final arrays as the one-launch-per-step paths, at any G.  bucket: the bags counted
+        exactly in O(n + m) on their integer images (algo="sorted") instead of all pairs — the
+        same integers.
         rng = (B, seed): the incomplete statistic (UnNB_many over ranks, cs.UnNBT's loop,
         compute_stats.py:119-123): the received records are written at their EXACT positions
         (tw_chain_unpack_exact) — the device draws address positions — and B pairs per bag are
         drawn and counted on the images (tw_count_pairs_chain_rng, step t keyed seed + t), the
-        integers of count_rng on the same permuted arrays."""
+        integers of count_rng on the same permuted arrays.
+
+        Streams (the whole cross-stream contract of the call):
+          main           the ranking, emissions, collectives of the chunks, unpacks, counts.
+          _guard_stream  the verdict hash of a carried call: forked at the call's start
+                         (waits for main), joined by main before the counts' reduction / the
+                         host's read of the verdict (_join_guard).
+          _final_stream  ONE fork per call, enqueued after the last count and waiting on an
+                         event recorded on main right behind the last emission (the chains'
+                         final positions are written): over ranks the final exchange
+                         (_final_exchange, event `emitted`), in one process the final scatters
+                         (_final_scatter, event `fork`, FINAL_BESIDE_COUNT).  Main joins it
+                         before taking the final arrays."""
         t, ops, G, r = self.t, self.ops, self.G, self.rank
         n, m, N = self.n_loc, self.m_loc, self.N
         dev = self.X.device
         half = self.pred == L.TW_PRED_HALF
         coll = self.coll  # the exchange branch (several ranks, or forced at world size 1)
-        works = []  # the asynchronous all-gathers the final arrays wait for
         rec = self._carried(half) if use_carry else None
         carried = rec is not None
         verdict = None
@@ -1125,71 +1086,30 @@ class ShardedSample:
                         verdict.record_stream(gs)  # (made on the main stream, written on gs)
                 else:
                     self._checksum(cs, verdict, 1, self.G + 1 if coll else 0)
-        # over ranks the call's final arrays and carried records come by ONE exchange of the
-        # walked elements to the ranks holding their final positions (FINAL_EXCHANGE,
-        # tw_chain_final_pack / _scatter) instead of the all-gathers of X and of both record
-        # arrays and the inverse-chain gathers from them
-        fin_x = coll and FINAL_EXCHANGE and hasattr(ops, "chain_final_pack")
-        X0 = Z0 = None
+        M64 = 2 ** 64 - 1
+        X0 = Z0 = zw = None
         if coll:
-            # the ranking needs the whole Z now (unless the images are carried); without the
-            # final exchange the whole X (and Z) only for the final arrays (chain_gather), so
-            # those all-gathers run asynchronously under the chunks' counts
+            # the ranking needs the whole Z now, unless the images are carried: then its
+            # all-gather runs asynchronously and unused under the chunks' counts
             # (every rank gathers Z, carried or not: a rank whose sample changed alone ranks
             # afresh while the others carry, and the ranks' collectives must stay one sequence)
             if not carried:
                 Z0 = self._all_gather(self.Z)
             else:
-                Z0, w = self._all_gather(self.Z, async_op=True)
-                works.append(w)
-            if not fin_x:
-                X0, w = self._all_gather(self.X, async_op=True)
-                works.append(w)
+                Z0, zw = self._all_gather(self.Z, async_op=True)
         else:
             X0, Z0 = self.X, self.Z
         if not carried:
             rec = ops.rank_images_query(Z0, self.X, self.Z, self.dtype, half)
-        if rec is None:
-            for w in works:
-                w.wait()
+        if rec is None:  # (a fresh ranking: no all-gather is in flight)
+            if rng is not None:
+                return [self.UnNB(rng[0], (rng[1] + i) & M64, k) for i, k in enumerate(keys)]
             return [self.UnN(k) for k in keys]
         xr, zr = rec
-        RX = RZ = None
-        if coll and CARRY_IMAGES and not fin_x:
-            # the records follow their elements: gathered by the same inverse chains as the
-            # scores, from every rank's records (asynchronous, under the counts)
-            RX, w = self._all_gather(xr, async_op=True)
-            works.append(w)
-            RZ, w = self._all_gather(zr, async_op=True)
-            works.append(w)
         T = len(keys)
         C = min(T, CHAIN_MAX)
-        M64 = 2 ** 64 - 1
         kxs = [(2 * k) & M64 for k in keys]
         kzs = [(2 * k + 1) & M64 for k in keys]
-        final = None
-        if coll and self.X.is_cuda and not fin_x:
-            # the final arrays depend on the keys and the all-gathered sample only: gathered on
-            # a side stream beside the emission, exchanges and counts (not after them)
-            main = t.cuda.current_stream()
-            if getattr(self, "_final_stream", None) is None:
-                self._final_stream = t.cuda.Stream()
-            fs = self._final_stream
-            fs.wait_stream(main)
-            with t.cuda.stream(fs):
-                for w in works:
-                    if w is not None:
-                        w.wait()
-                works = []
-                final = ops.chain_gather(X0, Z0, r * n, n, r * m, m, kxs, kzs, RX, RZ)
-                for a in final:
-                    a.record_stream(main)
-        early = fin_x and FINAL_EARLY and hasattr(ops, "chain_walk")
-        if early:
-            # the final positions walked without emitting (tw_chain_walk), so the final
-            # exchange forks now, beside the whole call's emissions and counts (its all-to-all
-            # is issued before the chunks' on every rank: one collective order)
-            final = self._final_exchange(xr, zr, walk=(kxs, kzs))
         kx = int(n / N)
         kz = int((n + m) / N) - kx  # prop_swor_layout's shard sizes
         z_total = G * m  # the Z the images were ranked against: images <= z_total
@@ -1211,25 +1131,19 @@ class ShardedSample:
         zpos = self._work("zpos", (m,), t.int32)
         counts = t.empty((T, N), dtype=t.int64, device=dev)
         if coll:
-            # one all-to-all per chunk (CHAIN_SUB = 0), or the chunk's steps in sub-chunks of
-            # <= CHAIN_SUB steps, each with its own send / receive buffers and its own async
-            # all-to-all: every sub-chunk's emission is enqueued first, then each sub-chunk
-            # waits for its records, unpacks and counts
+            # one all-to-all per chunk, its unpack and ONE count launch behind it
             tot = n + m
             cap = max(1, tot // G + tot // (8 * G) + 1024)
             W = 2 if half else 1
-            Sub = max(1, min(CHAIN_SUB, -(-C // 2))) if CHAIN_SUB > 0 else C
-            nsub = -(-C // Sub)
-            # the send / receive ring persists on the sample across calls (fresh
+            # the send / receive buffers persist on the sample across calls (fresh
             # GB-scale allocations per call made the caching allocator flush and re-map)
-            rk = (G, Sub, cap, W, nsub)
+            rk = (G, C, cap, W)
             ring = getattr(self, "_chain_ring", None)
             if ring is None or ring[0] != rk:
-                self._chain_ring = None  # release the old ring first
-                sends = [t.empty((G * Sub * (cap + 1) * W,), dtype=t.int64, device=dev)
-                         for _ in range(nsub)]
-                self._chain_ring = ring = (rk, sends, [t.empty_like(b) for b in sends])
-            sends, recvs = ring[1], ring[2]
+                self._chain_ring = None  # release the old buffers first
+                send = t.empty((G * C * (cap + 1) * W,), dtype=t.int64, device=dev)
+                self._chain_ring = ring = (rk, send, t.empty_like(send))
+            send, recv = ring[1], ring[2]
             if getattr(self, "_chain_flag", None) is None:
                 self._chain_flag = t.zeros((1,), dtype=t.int32, device=dev)
         else:
@@ -1238,55 +1152,37 @@ class ShardedSample:
         for i0 in range(0, T, C):
             c = min(C, T - i0)
             if coll:
-                # with sub-chunks, the emissions (and the all-to-alls issued behind them) on a
-                # side stream, so sub-chunk j+1's emission runs beside sub-chunk j's count; the
-                # side stream first waits for the main stream (the previous chunk's unpacks and
-                # counts are done with these send / receive buffers)
-                es = None
-                if self.X.is_cuda and c > Sub:
-                    if getattr(self, "_emit_stream", None) is None:
-                        self._emit_stream = t.cuda.Stream()
-                    es = self._emit_stream
-                    es.wait_stream(t.cuda.current_stream())
-                xchg = []
-                with (t.cuda.stream(es) if es is not None else contextlib.nullcontext()):
-                    for j, a in enumerate(range(0, c, Sub)):
-                        cs = min(Sub, c - a)
-                        ops.chain_emit(xr, zr, half, xpos, zpos, i0 == 0 and a == 0, r, G,
-                                       kxs[i0 + a:i0 + a + cs], kzs[i0 + a:i0 + a + cs], kx, kz,
-                                       N, send=sends[j], cap=cap, flag=self._chain_flag)
-                        sz = G * cs * (cap + 1) * W
-                        xchg.append((a, cs, j, self._all_to_all(recvs[j][:sz], sends[j][:sz],
-                                                                async_op=True)))
-                    emitted = None
-                    if fin_x and not early and i0 + c >= T and self.X.is_cuda:
-                        # the final exchange (enqueued after the last count) waits for this
-                        # event only: the chains' final positions, not the counts
-                        emitted = t.cuda.Event()
-                        emitted.record()
-                for a, cs, j, work in xchg:
-                    if work is not None:
-                        work.wait()
-                    if rng is None and not bucket and hasattr(ops, "chain_unpack_count"):
-                        # the receive side in one native call (unpack + count)
-                        with _bounded(ops, z_total):
-                            ops.chain_unpack_count(recvs[j], G, cs, cap, half, n, m,
-                                                   x_bag[a:a + cs], z_bag[a:a + cs],
-                                                   self._chain_flag, kx, kz, N, self.x_off_dev,
-                                                   self.z_off_dev, self.max_nx, self.max_nz,
-                                                   counts[i0 + a:i0 + a + cs])
-                        continue
+                last = i0 + c >= T
+                ops.chain_emit(xr, zr, half, xpos, zpos, i0 == 0, r, G, kxs[i0:i0 + c],
+                               kzs[i0:i0 + c], kx, kz, N, send=send, cap=cap,
+                               flag=self._chain_flag)
+                sz = G * c * (cap + 1) * W
+                work = self._all_to_all(recv[:sz], send[:sz], async_op=True)
+                emitted = None
+                if last and self.X.is_cuda:
+                    # the final exchange (enqueued after the last count) waits for this event
+                    # only: the chains' final positions, not the chunk's exchange or count
+                    emitted = t.cuda.Event()
+                    emitted.record()
+                if work is not None:
+                    work.wait()
+                xb, zb, out = x_bag[:c], z_bag[:c], counts[i0:i0 + c]
+                if rng is None and not bucket and hasattr(ops, "chain_unpack_count"):
+                    # the receive side in one native call (unpack + count)
+                    with _bounded(ops, z_total):
+                        ops.chain_unpack_count(recv, G, c, cap, half, n, m, xb, zb,
+                                               self._chain_flag, kx, kz, N, self.x_off_dev,
+                                               self.z_off_dev, self.max_nx, self.max_nz, out)
+                else:
                     if rng is not None:
-                        ops.chain_unpack_exact(recvs[j], G, cs, cap, n, m, x_bag[a:a + cs],
-                                               z_bag[a:a + cs], self._chain_flag)
+                        ops.chain_unpack_exact(recv, G, c, cap, n, m, xb, zb, self._chain_flag)
                     else:
-                        ops.chain_unpack(recvs[j], G, cs, cap, half, n, m, x_bag[a:a + cs],
-                                         z_bag[a:a + cs], self._chain_flag, kx, kz, N)
-                    count(x_bag[a:a + cs], z_bag[a:a + cs], cs, counts[i0 + a:i0 + a + cs],
-                          i0 + a)
-                if fin_x and not early and i0 + c >= T:
+                        ops.chain_unpack(recv, G, c, cap, half, n, m, xb, zb,
+                                         self._chain_flag, kx, kz, N)
+                    count(xb, zb, c, out, i0)
+                if last:
                     # the walked elements' final positions are known once the call's last
-                    # emission ran: their exchange runs on a side stream beside the last
+                    # emission ran: their exchange runs on the final stream beside the last
                     # chunk's count — enqueued AFTER that count, so the host's work for it
                     # never delays the count's launch (the collectives keep one order: the
                     # chunk's all-to-all was issued first on every rank)
@@ -1307,21 +1203,12 @@ class ShardedSample:
                 scattered = self._final_scatter(X0, Z0, xr, zr, xpos, zpos, fork)
         carry = None
         if coll:
-            if final is not None:
-                if self.X.is_cuda:
-                    t.cuda.current_stream().wait_stream(self._final_stream)
-                for w in works:  # (fin_x: the Z all-gather of a carried call, unused)
-                    if w is not None:
-                        w.wait()
-                if fin_x and CARRY_IMAGES:
-                    RX = xr  # (marks the carry: the records came with the final exchange)
-            else:
-                for w in works:
-                    if w is not None:
-                        w.wait()
-                final = ops.chain_gather(X0, Z0, r * n, n, r * m, m, kxs, kzs, RX, RZ)
+            if self.X.is_cuda:
+                t.cuda.current_stream().wait_stream(self._final_stream)
+            if zw is not None:  # (the Z all-gather of a carried call, unused)
+                zw.wait()
             self.X, self.Z = final[0], final[1]
-            if RX is not None:
+            if CARRY_IMAGES:  # (the records came with the final exchange)
                 carry = (final[2], final[3])
             self._join_guard()
             counts = self._reduce_counts(counts, carried=verdict if verdict is not None
@@ -1377,47 +1264,35 @@ class ShardedSample:
         if gs is not None:
             self.t.cuda.current_stream().wait_stream(gs)
 
-    def _final_exchange(self, xr, zr, xpos=None, zpos=None, es=None, walk=None):
-        """The call's final arrays over ranks (FINAL_EXCHANGE): on the final stream, this
-        rank's walked elements — scores self.X / self.Z, records xr / zr — packed into G
-        fixed-capacity buckets of 24-B records by their final positions (tw_chain_final_pack),
-        ONE equal-split all-to-all, and every received record written at its position
-        (tw_chain_final_scatter): (X, Z, X records, Z records) of the rank's final positions,
-        recorded for the main stream.  The final positions: walk = (keys_x, keys_z), the
-        call's chains walked here without emitting (tw_chain_walk, at the call's start), or
-        xpos / zpos, the chain state after the call's last emission (`es`: the stream it ran
-        on, or an event recorded after it)."""
+    def _final_exchange(self, xr, zr, xpos, zpos, emitted):
+        """The call's final arrays over ranks: on the final stream, this rank's walked
+        elements — scores self.X / self.Z, records xr / zr — packed into G fixed-capacity
+        buckets of 24-B records by their final positions xpos / zpos, the chain state after
+        the call's last emission (tw_chain_final_pack), ONE equal-split all-to-all, and every
+        received record written at its position (tw_chain_final_scatter): (X, Z, X records,
+        Z records) of the rank's final positions, recorded for the main stream.  emitted: the
+        event recorded on the main stream behind the last emission (None for host tensors),
+        the only thing the final stream waits for."""
         t, G, n, m = self.t, self.G, self.n_loc, self.m_loc
-        main = t.cuda.current_stream() if self.X.is_cuda else None
+        main = t.cuda.current_stream() if emitted is not None else None
         tot = n + m
         cap = max(1, tot // G + tot // (8 * G) + 1024)
         send = self._work("fin_send", (G * (cap + 1) * 3,), t.int64)
         recv = self._work("fin_recv", (G * (cap + 1) * 3,), t.int64)
         if getattr(self, "_chain_flag", None) is None:
             self._chain_flag = t.zeros((1,), dtype=t.int32, device=self.X.device)
-        if main is None:
-            fs = None
-        else:
+        fs = None
+        if emitted is not None:
             if getattr(self, "_final_stream", None) is None:
                 self._final_stream = t.cuda.Stream()
             fs = self._final_stream
-            if isinstance(es, t.cuda.Event):  # the last emission's completion (enqueued later)
-                fs.wait_event(es)
-            else:
-                fs.wait_stream(main)
-                if es is not None:
-                    fs.wait_stream(es)
+            fs.wait_event(emitted)
         with (t.cuda.stream(fs) if fs is not None else contextlib.nullcontext()):
             # the cursors (zero on entry, left zero by the pack): made on the final stream, so
             # their zeroing is ordered before the pack whatever that stream waits for
             cur = getattr(self, "_fin_cursor", None)
             if cur is None or cur.numel() != G:
                 cur = self._fin_cursor = t.zeros((G,), dtype=t.int64, device=self.X.device)
-            if walk is not None:
-                xpos = self._work("fin_xpos", (n,), t.int32)
-                zpos = self._work("fin_zpos", (m,), t.int32)
-                self.ops.chain_walk(self.rank * n, n, G * n, self.rank * m, m, G * m, walk[0],
-                                    walk[1], xpos, zpos)
             self.ops.chain_final_pack(self.X, xr, xpos, self.Z, zr, zpos, G, cap, cur, send,
                                       self._chain_flag)
             self._all_to_all(recv, send)
