@@ -5,9 +5,11 @@
 //   cs.Un(kernel="gini")   compute_stats.py:17-18   mean(|X_col - Z_row|)
 //   conv_AUC(margin)       compute_stats.py:129-135 mean(max(Z_row - X_col + margin, 0))
 //   UB_indices prod/gini   compute_stats.py:26-29 ; conv_AUC_deter_pairs compute_stats.py:137-144
-// NumPy reduces these with pairwise summation; the parity bar is a relative tolerance
-// (tests/test_pairsum.py), not bits.  Sums here are deterministic: each block writes one
-// partial in a fixed lane/wave order and a second kernel adds a shard's partials in order.
+// NumPy reduces these with pairwise summation; the parity bar is a tolerance from the longest
+// accumulation chain times the sum of |terms| (tests/test_gpu_pairsum.py), not bits — and never
+// relative to the result, which a prod sum cancels.  Sums here are deterministic: each block
+// writes one partial in a fixed lane/wave order and a second kernel adds a shard's partials in
+// order.
 #include "tw_common.h"
 #include <algorithm>
 
