@@ -1005,6 +1005,59 @@ int tw_shuffle_swaps_part(uint64_t* d_x, int64_t nx, uint64_t* d_z, int64_t nz,
                           int32_t r_end, int32_t last, void* d_work, uint32_t* d_pending,
                           void* stream);
 
+/* ---- MT19937 jump-ahead and NumPy-order randint streams on the device (csrc/mtjump.cpp host,
+ * csrc/mtdraw.hip device).  The draws are those of consecutive legacy
+ * np.random.randint(low, high, size) calls — cs.UB's two calls per block
+ * (compute_stats.py:37-42) — made from NumPy's own MT19937 state without the indices crossing
+ * PCIe: MT19937 is linear over GF(2), so the state J words ahead is a polynomial t^J mod phi in
+ * the transition applied to the current state (Haramoto, Matsumoto, Nishimura, Panneton,
+ * L'Ecuyer 2008), phi the degree-19937 minimal polynomial of the word recurrence (Matsumoto &
+ * Nishimura 1998); for a fixed bound legacy randint is a masked rejection on consecutive
+ * 32-bit words, i.e. a stream compaction of the raw words.
+ * Polynomials are bit-packed in 312 uint64 (bit k = coefficient of t^k).
+ * tw_mt_minpoly: phi (Berlekamp-Massey over GF(2), once per process).  tw_mt_jump_poly: t^J mod
+ * phi, J >= 0.  tw_mt_poly_mulmod: a * b mod phi (reduced operands; out may alias).
+ * tw_mt_jump_host: a NumPy (key[624], pos) state advanced by exactly J words, in NumPy's
+ * representation (what J genrand_int32 calls leave).  Host entries return 0, 1 on bad arguments,
+ * 2 if phi could not be found. */
+int tw_mt_minpoly(uint64_t* out);
+int tw_mt_jump_poly(int64_t J, uint64_t* out);
+int tw_mt_poly_mulmod(const uint64_t* a, const uint64_t* b, uint64_t* out);
+int tw_mt_jump_host(uint32_t* key, int32_t* pos, int64_t J);
+/* Sub-stream states by doubling.  With x[i] the raw word sequence aligned to the host state
+ * (x[0..623] = key) and L = 624 * stream_blocks, d_table[n_states][624] receives row 0 = key and
+ * row k >= 1 = x[kL - 1 .. kL + 622] (the window one word BEFORE the sub-stream: its word 0
+ * carries only the top bit, and x[kL + 623] follows by one recurrence step — the low 31 bits of a
+ * window's word 0 are not state).  Level v makes rows [2^v, 2^(v+1)) from rows [0, 2^v), one
+ * workgroup per row: d_polys[levels][2][19968] holds t^(2^v L - 1) (applied to row 0) and
+ * t^(2^v L) (applied to the others), each as the LIST of its set coefficients: word 0 = the
+ * number of listed positions (a multiple of 16, <= 19952), words 16.. = the positions, padded
+ * with 20560 (a zero word of the kernel's sequence); levels >= ceil(log2 n_states). */
+int tw_mt_states(const uint32_t* key, int32_t n_states, const uint32_t* d_polys, int32_t levels,
+                 uint32_t* d_table, void* stream);
+/* The tempered words x[0 .. n_states * L) of a state table into d_words, and for each of the
+ * n_cfg <= 4 (mask, range) configurations the number of words of every key block (624 words)
+ * with (w & mask) <= range into d_counts[n_cfg][n_states * stream_blocks]. */
+int tw_mt_generate(const uint32_t* d_table, int32_t n_states, int32_t stream_blocks,
+                   int32_t n_cfg, const uint32_t* cfg_mask, const uint32_t* cfg_rng,
+                   uint32_t* d_words, uint32_t* d_counts, void* stream);
+/* One round of n_calls consecutive masked-rejection randint calls on the words of a state table
+ * made from (key, *pos): call c draws call_cnt[c] values v = w & cfg_mask[f] <= cfg_rng[f],
+ * f = call_cfg[c], from the words that follow call c - 1's last one (the first call starts at
+ * word *pos), and writes int32 call_base[c] + v at d_out[call_out[c] ...] (d_out: out_len
+ * entries).  progress[0..2] = calls completed, values written of the first incomplete call,
+ * words consumed; (key, *pos) is advanced past the consumed words in NumPy's representation.
+ * A round whose words run out leaves the rest to the next round (a fresh table from the new
+ * state).  Synchronises the stream.  d_work: tw_np_randint_dev_work_bytes bytes. */
+int64_t tw_np_randint_dev_work_bytes(int32_t n_states, int32_t stream_blocks, int32_t n_calls,
+                                     int32_t n_cfg);
+int tw_np_randint_dev(uint32_t* key, int32_t* pos, const uint32_t* d_table, int32_t n_states,
+                      int32_t stream_blocks, int32_t n_calls, const int32_t* call_cfg,
+                      const int64_t* call_cnt, const int32_t* call_base, const int64_t* call_out,
+                      int32_t n_cfg, const uint32_t* cfg_mask, const uint32_t* cfg_rng,
+                      int32_t* d_out, int64_t out_len, void* d_work, int64_t* progress,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ import numpy as np
 from . import _engine as E
 from . import _lib as L
 from . import _multi as M
+from . import numpy_rng
 from .numpy_rng import shuffle_pair
 
 
@@ -317,8 +318,11 @@ class Incomplete(BlockSpec):
         self.kernel = kernel
 
     def draw(self, nx, nz):
-        ix = np.random.randint(0, nx, self.B)
-        iz = np.random.randint(0, nz, self.B)
+        try:  # the same two calls (values and state) in one native call
+            ix, iz = numpy_rng.randint_batch([(0, nx, self.B), (0, nz, self.B)])
+        except NotImplementedError:  # the global generator is not the legacy MT19937
+            ix = np.random.randint(0, nx, self.B)
+            iz = np.random.randint(0, nz, self.B)
         return ix, iz
 
     def work(self, nx, nz, dtype):
@@ -345,20 +349,60 @@ class Incomplete(BlockSpec):
     def evaluate_device(self, xd, zd, blocks):
         """evaluate() on float64 device arrays of 1-D samples (the device-shuffle path of
         run_un_repeated): the blocks laid out as in block_indexed_values, the draws shifted."""
-        ix_loc = [np.asarray(b.aux[0], dtype=np.int64) for b in blocks]
-        iz_loc = [np.asarray(b.aux[1], dtype=np.int64) for b in blocks]
-        offs = np.concatenate([[0], np.cumsum([len(a) for a in ix_loc])]).astype(np.int64)
-        npairs = np.diff(offs)
         xa, xo = _layout(xd, blocks, "x")
         za, zo = _layout(zd, blocks, "z")
-        ix = np.concatenate([a + o for a, o in zip(ix_loc, xo[:-1])])
-        iz = np.concatenate([a + o for a, o in zip(iz_loc, zo[:-1])])
+        if all(isinstance(b.aux, DeviceDraws) for b in blocks):
+            # drawn on the device at absolute positions of this layout (int32, resident)
+            offs = np.arange(len(blocks) + 1, dtype=np.int64) * self.B
+            ix = _join_draws([(b.aux.out, b.aux.x_at) for b in blocks], self.B)
+            iz = _join_draws([(b.aux.out, b.aux.z_at) for b in blocks], self.B)
+            # (blocks that are not consecutive slices were gathered by _layout: moved there)
+            ix = _shift_draws(ix, [b.x[0] for b in blocks], xo, self.B)
+            iz = _shift_draws(iz, [b.z[0] for b in blocks], zo, self.B)
+        else:
+            ix_loc = [np.asarray(b.aux[0], dtype=np.int64) for b in blocks]
+            iz_loc = [np.asarray(b.aux[1], dtype=np.int64) for b in blocks]
+            offs = np.concatenate([[0], np.cumsum([len(a) for a in ix_loc])]).astype(np.int64)
+            ix = np.concatenate([a + o for a, o in zip(ix_loc, xo[:-1])])
+            iz = np.concatenate([a + o for a, o in zip(iz_loc, zo[:-1])])
+        npairs = np.diff(offs)
         if self.kernel == "AUC":
             counts = E.count_indexed(xa, za, L.TW_F64, ix, iz, offs, "gt", spans=(xo, zo))
             return [E.ratio(c, p) for c, p in zip(counts, npairs)]
         kern = {"prod": L.TW_KERN_PROD, "gini": L.TW_KERN_GINI}[self.kernel]
         sums = E.pair_sum_indexed(xa, za, ix, iz, offs, kern)
         return [np.float64(s / np.float64(p)) for s, p in zip(sums, npairs)]
+
+
+class DeviceDraws:
+    """A block's B index pairs drawn on the device (numpy_rng.randint_device): absolute int32
+    positions out[x_at : x_at + B] / out[z_at : z_at + B] in the device-shuffle layout."""
+    __slots__ = ("out", "x_at", "z_at")
+
+    def __init__(self, out, x_at, z_at):
+        self.out, self.x_at, self.z_at = out, x_at, z_at
+
+
+def _join_draws(parts, B: int):
+    """The (tensor, start) parts of B entries each as one index tensor: runs that are
+    consecutive in one tensor are slices of it, and only different runs are concatenated."""
+    runs = []
+    for out, at in parts:
+        if runs and runs[-1][0] is out and runs[-1][2] == at:
+            runs[-1][2] = at + B
+        else:
+            runs.append([out, at, at + B])
+    views = [out[a:b] for out, a, b in runs]
+    return views[0] if len(views) == 1 else L.torch().cat(views)
+
+
+def _shift_draws(idx, starts, off, B: int):
+    """Device draws made at absolute positions `starts` of the blocks, moved to a layout whose
+    blocks start at off[:-1] (nothing to do when the layout is the sample itself)."""
+    delta = np.asarray(off[:-1], dtype=np.int64) - np.asarray(starts, dtype=np.int64)
+    if not delta.any():
+        return idx
+    return idx + L.to_device(delta, np.int32).repeat_interleave(B)
 
 
 def block_indexed_values(x: np.ndarray, z: np.ndarray, blocks: list, ix_loc: list,
@@ -436,11 +480,15 @@ def indexed_values(x: np.ndarray, z: np.ndarray, ix: np.ndarray, iz: np.ndarray,
     return [cast(s / np.float64(p)) for s, p in zip(sums, npairs)]
 
 
-def plan_un(X, Z, N, spec, sampling_type, variant: str, shuffle=shuffle_pair) -> list:
+def plan_un(X, Z, N, spec, sampling_type, variant: str, shuffle=shuffle_pair,
+            draw=None) -> list:
     """The host half of UN (compute_stats.py:56-92 "cs", estimation-experiment/main.py:33-69
     "est"): shuffle X and Z in place, then walk the N blocks making every RNG draw of the
     reference in order.  Returns the plan [("val", Block) | ("zero",)] in append order.
-    shuffle(X, Z): the in-place shuffles (or, for the device path, only their draws)."""
+    shuffle(X, Z): the in-place shuffles (or, for the device path, only their draws).
+    draw(nx, nz): what makes a block's aux in place of spec.draw (the device draws record the
+    sizes and draw all blocks afterwards: nothing else is drawn between prop-SWOR blocks)."""
+    draw = spec.draw if draw is None else draw
     X_rem = X
     Z_rem = Z
     shuffle(X_rem, Z_rem)  # np.random.shuffle(X); np.random.shuffle(Z), bit for bit
@@ -467,7 +515,7 @@ def plan_un(X, Z, N, spec, sampling_type, variant: str, shuffle=shuffle_pair) ->
                 xs = (x_pos, min(x_pos + k, X_rem.shape[0]))
                 zs = (z_pos, min(z_pos + tau - k, Z_rem.shape[0]))
                 blk = Block(xs, zs)
-                blk.aux = spec.draw(blk.nx(), blk.nz())
+                blk.aux = draw(blk.nx(), blk.nz())
                 plan.append(("val", blk))
             x_pos = min(x_pos + k, X_rem.shape[0])
             z_pos = min(z_pos + (tau - k), Z_rem.shape[0])
@@ -620,6 +668,13 @@ STREAM_LAST_SHUFFLE = 4
 # ... and the uploads, swap-round launches and count enqueues made on a launcher thread
 # (_engine.launcher), off the thread that makes the draws
 THREADED_LAUNCHES = True
+# the incomplete drop-in's block draws (prop-SWOR: 2N consecutive randint calls a repetition)
+# made on the device from NumPy's own MT19937 stream (numpy_rng.randint_device, DESIGN.md
+# §4.4c) when a repetition draws at least DEVICE_DRAWS_MIN indices: the smallest measured
+# batch at which the device draws alone beat the native host draws (2^21: 1.15 ms against
+# 0.91 ms; 2^22: 1.83 against 2.78 — tools/time_unnbt_dropin.py, profiles/time_unnbt_dropin.json)
+DEVICE_DRAWS = True
+DEVICE_DRAWS_MIN = 1 << 22
 
 
 def _mark(label):
@@ -685,9 +740,14 @@ def _run_un_repeated_device(X, Z, N, spec, sampling_type, variant: str, T: int):
     cs = E.side_stream("count") if early else None
     pending = {}
     nx, nz = X.shape[0], Z.shape[0]
+    dev_draws = (DEVICE_DRAWS and type(spec) is Incomplete and sampling_type == "prop-SWOR"
+                 and 2 * N * spec.B >= DEVICE_DRAWS_MIN)
     for k in range(T):
         step[0] = k
-        plans.append(plan_un(X, Z, N, spec, sampling_type, variant, shuffle=draws))
+        plans.append(plan_un(X, Z, N, spec, sampling_type, variant, shuffle=draws,
+                             draw=(lambda bx, bz: (bx, bz)) if dev_draws else None))
+        if dev_draws:
+            _draw_step_on_device(plans[k], spec, k * nx, k * nz)
         if early and k < T - 1:  # step k's counts beside the host's next draws
             def count(k=k):  # after step k's pushes (on the launcher thread when threaded)
                 blks = [p[1] for p in plans[k] if p[0] == "val"]
@@ -748,6 +808,26 @@ def _run_un_repeated_device(X, Z, N, spec, sampling_type, variant: str, T: int):
     for k, done in pending.items():
         by_step[k] = done()
     return np.mean([finish_un(plans[k], by_step[k]) for k in range(T)])
+
+
+def _draw_step_on_device(plan, spec, x0: int, z0: int) -> None:
+    """The block draws of one repetition's plan (plan_un recorded each block's (nx, nz)), in
+    the reference's order — randint(0, nx, B) then randint(0, nz, B) per block — as ONE device
+    batch: block-local draws land as absolute positions of the device-shuffle layout (the
+    repetition's samples start at x0 / z0), all X draws in one run and all Z draws in another.
+    Returns with NumPy's state advanced past them.  What the device path does not serve is
+    drawn on the host, from the same state."""
+    blks = [p[1] for p in plan if p[0] == "val"]
+    B, nb = spec.B, len(blks)
+    calls, add, at = [], [], []
+    for i, b in enumerate(blks):
+        bx, bz = b.aux
+        calls += [(0, bx, B), (0, bz, B)]
+        add += [x0 + b.x[0], z0 + b.z[0]]
+        at += [i * B, (nb + i) * B]
+    got = numpy_rng.randint_device(calls, add, out_offsets=at) if blks else None
+    for i, b in enumerate(blks):
+        b.aux = spec.draw(*b.aux) if got is None else DeviceDraws(got[0], i * B, (nb + i) * B)
 
 
 def evaluate_many(spec, jobs) -> list:

@@ -221,6 +221,15 @@ _SIGNATURES = {
     "tw_shuffle_swaps": [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "tw_shuffle_swaps_windows": [],
     "tw_shuffle_swaps_part": [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "tw_mt_minpoly": [_vp],
+    "tw_mt_jump_poly": [_i64, _vp],
+    "tw_mt_poly_mulmod": [_vp, _vp, _vp],
+    "tw_mt_jump_host": [_vp, _vp, _i64],
+    "tw_mt_states": [_vp, _i32, _vp, _i32, _vp, _vp],
+    "tw_mt_generate": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "tw_np_randint_dev_work_bytes": [_i32, _i32, _i32, _i32],
+    "tw_np_randint_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                          _vp, _i64, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -236,6 +245,7 @@ _RESTYPES = {
     "tw_shuffle_swaps_work_bytes": ctypes.c_int64,
     "tw_eval_small_work": ctypes.c_int64,
     "tw_words_checksum_acc_words": ctypes.c_int64,
+    "tw_np_randint_dev_work_bytes": ctypes.c_int64,
 }
 
 _lib = None

@@ -8,6 +8,8 @@ Only the MT19937-backed legacy global RandomState is supported (what the referen
 from __future__ import annotations
 
 import ctypes
+import functools
+import math
 
 import numpy as np
 
@@ -41,9 +43,11 @@ class _CopiedState:
     """get_state/set_state around a native call: the fallback when _mt_state() is None."""
 
     def __init__(self):
-        name, key, pos, self.has_gauss, self.gauss = np.random.get_state(legacy=True)
-        if name != "MT19937":
+        st = np.random.get_state(legacy=False)  # (a dict whatever the bit generator)
+        if st["bit_generator"] != "MT19937":
             raise NotImplementedError("only the MT19937 legacy RandomState is supported")
+        key, pos = st["state"]["key"], st["state"]["pos"]
+        self.has_gauss, self.gauss = st["has_gauss"], st["gauss"]
         self.key = np.ascontiguousarray(key, dtype=np.uint32).copy()
         self.pos = ctypes.c_int32(int(pos))
 
@@ -83,6 +87,218 @@ def randint_batch(calls) -> list:
         raise ValueError("high <= low")
     offs = np.concatenate([[0], np.cumsum(cnt)])
     return [out[offs[i]:offs[i + 1]] for i in range(len(cnt))]
+
+
+# ----------------------------------------------------------------- MT19937 jump-ahead (host)
+_POLY_WORDS = 312  # a polynomial over GF(2) of degree <= 19937, bit-packed in uint64
+
+
+def mt_minpoly() -> np.ndarray:
+    """phi(t), the degree-19937 minimal polynomial of the MT19937 word recurrence (bit k of
+    the 312 uint64 = coefficient of t^k), by Berlekamp-Massey in csrc/mtjump.cpp."""
+    out = np.zeros(_POLY_WORDS, dtype=np.uint64)
+    if L.lib().tw_mt_minpoly(out.ctypes.data):
+        raise RuntimeError("tw_mt_minpoly failed")
+    return out
+
+
+@functools.lru_cache(maxsize=256)
+def mt_jump_poly(J: int) -> np.ndarray:
+    """t^J mod phi(t) (read-only, cached): applied to an MT19937 state it advances it J words."""
+    out = np.zeros(_POLY_WORDS, dtype=np.uint64)
+    if J < 0 or L.lib().tw_mt_jump_poly(int(J), out.ctypes.data):
+        raise ValueError(f"mt_jump_poly: bad jump {J}")
+    out.flags.writeable = False
+    return out
+
+
+def mt_poly_mul(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """a * b mod phi for reduced polynomials."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    out = np.zeros(_POLY_WORDS, dtype=np.uint64)
+    if a.shape != (_POLY_WORDS,) or b.shape != (_POLY_WORDS,) or L.lib().tw_mt_poly_mulmod(
+            a.ctypes.data, b.ctypes.data, out.ctypes.data):
+        raise ValueError("mt_poly_mul: operands must be reduced 312-word polynomials")
+    return out
+
+
+def mt_jumped(key, pos: int, J: int):
+    """(key, pos) of np.random.get_state() advanced by exactly J words: what J genrand_int32
+    calls (RandomState.randint(0, 2**32, J, dtype=np.uint32)) leave, in NumPy's representation."""
+    k = np.array(key, dtype=np.uint32)  # a copy
+    p = ctypes.c_int32(int(pos))
+    if k.shape != (_RK_STATE_LEN,) or L.lib().tw_mt_jump_host(k.ctypes.data, ctypes.byref(p),
+                                                              int(J)):
+        raise ValueError(f"mt_jumped: bad state or jump (pos={pos}, J={J})")
+    return k, p.value
+
+
+# ------------------------------------------------------- randint streams drawn on the device
+# words per sub-stream = 624 * STREAM_BLOCKS (tools/time_unnbt_dropin.py sweeps it); words per
+# round (the word buffer's cap: 4 bytes each)
+STREAM_BLOCKS = 420
+ROUND_WORDS = 1 << 28
+# rounds made / calls served by randint_device (tests tell from it that the device path ran)
+DEVICE_DRAWS_STATS = {"rounds": 0, "calls": 0}
+_MAX_CONFIGS = 4
+_LEVEL_POLYS = {}  # stream_blocks -> [(t^(2^v L - 1), t^(2^v L)) for v = 0, 1, ...]
+_LEVEL_POLYS_DEV = {}  # (device, stream_blocks, levels) -> int32 device tensor [levels, 2, 19968]
+_POLY_CAP, _POLY_PAD = 19952, 20560  # listed positions a polynomial, the zero word's position
+
+
+def _poly_list(g: np.ndarray) -> np.ndarray:
+    """A bit-packed polynomial as tw_mt_states reads it: the count of listed positions (a
+    multiple of 16) in word 0, the positions of its set coefficients from word 16 on, padded
+    with the position of a zero word."""
+    at = np.nonzero(np.unpackbits(np.ascontiguousarray(g).view(np.uint8), bitorder="little"))[0]
+    row = np.full(16 + _POLY_CAP, _POLY_PAD, dtype=np.uint32)
+    row[0] = -(-len(at) // 16) * 16
+    row[16:16 + len(at)] = at
+    return row
+
+
+def _level_polys(stream_blocks: int, levels: int):
+    """The doubling's polynomials on the device: level v jumps by 2^v L words (successive
+    squarings of t^L), and by one word less from row 0 (the host key is a window AT its
+    offset, the other rows one word before theirs): that is the same polynomial divided by t."""
+    host = _LEVEL_POLYS.setdefault(stream_blocks, [])
+    if len(host) < levels:
+        phi = mt_minpoly()
+        while len(host) < levels:
+            g = (mt_poly_mul(host[-1][1], host[-1][1]) if host
+                 else np.array(mt_jump_poly(_RK_STATE_LEN * stream_blocks)))
+            h = g ^ phi if int(g[0]) & 1 else g  # g / t: phi's constant term is 1
+            h = (h >> np.uint64(1)) | (np.append(h[1:], np.uint64(0)) << np.uint64(63))
+            host.append((h, g))
+    dev = L.device()
+    key = (dev.index, stream_blocks, levels)
+    if key not in _LEVEL_POLYS_DEV:
+        flat = np.stack([np.stack([_poly_list(g) for g in p])
+                         for p in host[:levels]]).view(np.int32)
+        _LEVEL_POLYS_DEV[key] = L.to_device(flat)
+    return _LEVEL_POLYS_DEV[key]
+
+
+def mt_states(key, n_states: int, stream_blocks: int):
+    """The (n_states, 624) int32 device table of tw_mt_states for a host key (624 uint32)."""
+    k = np.ascontiguousarray(key, dtype=np.uint32)
+    return _mt_states_ptr(ctypes.c_void_p(k.ctypes.data), n_states, stream_blocks)
+
+
+def _mt_states_ptr(key_ptr, n_states: int, stream_blocks: int):
+    t = L.torch()
+    levels = max(0, int(n_states) - 1).bit_length()
+    polys = _level_polys(stream_blocks, levels) if levels else None
+    table = L.empty((int(n_states), _RK_STATE_LEN), t.int32)
+    L.call("tw_mt_states", key_ptr, int(n_states), L.ptr(polys), levels, L.ptr(table),
+           L.stream_handle())
+    return table
+
+
+def _masked_call(lo: int, hi: int, a: int):
+    """(range, mask) of one supported randint call, or None."""
+    rng = hi - 1 - lo
+    if rng < 0 or rng >= 0xFFFFFFFF or lo + a < -(1 << 31) or hi + a > (1 << 31):
+        return None
+    return rng, (1 << rng.bit_length()) - 1
+
+
+def randint_device(calls, add=None, *, stream_blocks=None, round_words=None, out_offsets=None):
+    """[np.random.randint(lo, hi, n) + add[c] for lo, hi, n in calls] drawn ON THE DEVICE from
+    NumPy's own legacy MT19937 stream (csrc/mtdraw.hip): returns (out, offsets)
+    — an int32 device tensor and the int64 start of every call's values in it (len(calls) + 1
+    entries; call order unless out_offsets places the calls) — and leaves np.random in exactly
+    the state those calls would leave it.  Returns None, having drawn nothing, for what the
+    device path does not serve: a global generator that is not the legacy MT19937, an empty
+    range, high-1-low >= 2^32-1, values beyond int32, more than 4 distinct (mask, range) pairs.
+    stream_blocks / round_words: key blocks per sub-stream and words per round (tuning and
+    tests)."""
+    t = L.torch()
+    calls = [(int(lo), int(hi), int(n)) for lo, hi, n in calls]
+    add = [0] * len(calls) if add is None else [int(a) for a in add]
+    if len(add) != len(calls) or any(n < 0 for _, _, n in calls):
+        raise ValueError("randint_device: one add per call, sizes >= 0")
+    if _mt_state() is None and np.random.get_state(legacy=False)["bit_generator"] != "MT19937":
+        return None
+    sb = int(STREAM_BLOCKS if stream_blocks is None else stream_blocks)
+    cap = int(ROUND_WORDS if round_words is None else round_words)
+    if sb < 1 or cap < 1:
+        raise ValueError("randint_device: stream_blocks and round_words must be positive")
+    Lw = _RK_STATE_LEN * sb
+    cnt = np.array([n for _, _, n in calls], dtype=np.int64)
+    if out_offsets is None:
+        offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        starts = offsets[:-1]
+    else:
+        starts = offsets = np.asarray(out_offsets, dtype=np.int64)
+        order = np.argsort(starts, kind="stable")
+        ends = (starts + cnt)[order]
+        if starts.shape != cnt.shape or (len(cnt) and (
+                starts[order][0] != 0 or np.any(starts[order][1:] != ends[:-1]))):
+            raise ValueError("randint_device: out_offsets must tile the output")
+    total = int(cnt.sum())
+    configs, draws, fills = [], [], []
+    for c, ((lo, hi, n), a) in enumerate(zip(calls, add)):
+        mc = _masked_call(lo, hi, a)
+        if mc is None:
+            return None
+        if n == 0:
+            continue
+        if mc[0] == 0:  # randint(low, low + 1): no draw
+            fills.append((c, lo + a))
+            continue
+        if mc not in configs:
+            configs.append(mc)
+        draws.append((configs.index(mc), n, lo + a, int(starts[c]), mc[0] / (mc[1] + 1.0)))
+    if len(configs) > _MAX_CONFIGS:
+        return None
+    out = L.empty((total,), t.int32)
+    for c, v in fills:
+        out[int(starts[c]):int(starts[c]) + int(cnt[c])] = v
+    DEVICE_DRAWS_STATS["calls"] += len(calls)
+    if not draws:
+        return out, offsets
+    cfg = np.array([d[0] for d in draws], dtype=np.int32)
+    rem = np.array([d[1] for d in draws], dtype=np.int64)
+    base = np.array([d[2] for d in draws], dtype=np.int64).astype(np.int32)
+    at = np.array([d[3] for d in draws], dtype=np.int64)
+    pacc = np.array([d[4] + 1.0 / (configs[d[0]][1] + 1.0) for d in draws])  # (range+1)/(mask+1)
+    cmask = np.array([m for _, m in configs], dtype=np.uint32)
+    crng = np.array([r for r, _ in configs], dtype=np.uint32)
+    lib = L.lib()
+    progress = (ctypes.c_int64 * 3)()
+
+    def rounds(key, pos):
+        pos_p = ctypes.cast(pos, ctypes.POINTER(ctypes.c_int32))
+        ci = 0
+        while ci < len(cfg):
+            # words this round: the expected number for every remaining draw plus six standard
+            # deviations of the rejected count, after the pos words of the current key block
+            want = float(np.sum(rem[ci:] / pacc[ci:]))
+            var = float(np.sum(rem[ci:] * (1.0 - pacc[ci:]) / pacc[ci:] ** 2))
+            p0 = int(pos_p[0])
+            S = int(math.ceil((p0 + want + 6.0 * math.sqrt(var) + 64.0) / Lw))
+            S = max(1, min(S, cap // Lw), p0 // Lw + 1)
+            table = _mt_states_ptr(key, S, sb)
+            n = len(cfg) - ci
+            work = L.empty((int(lib.tw_np_randint_dev_work_bytes(S, sb, n, len(configs))),),
+                           t.uint8)
+            c_cfg, c_rem = np.ascontiguousarray(cfg[ci:]), np.ascontiguousarray(rem[ci:])
+            c_base, c_at = np.ascontiguousarray(base[ci:]), np.ascontiguousarray(at[ci:])
+            L.call("tw_np_randint_dev", key, pos, L.ptr(table), S, sb, n, c_cfg.ctypes.data,
+                   c_rem.ctypes.data, c_base.ctypes.data, c_at.ctypes.data, len(configs),
+                   cmask.ctypes.data, crng.ctypes.data, L.ptr(out), total, L.ptr(work),
+                   ctypes.addressof(progress), L.stream_handle())
+            DEVICE_DRAWS_STATS["rounds"] += 1
+            ci += int(progress[0])
+            if ci < len(cfg):
+                rem[ci] -= int(progress[1])
+                at[ci] += int(progress[1])
+        return 0
+
+    _native_draws(rounds)
+    return out, offsets
 
 
 def _shuffle_items(a):
