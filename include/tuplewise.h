@@ -246,6 +246,27 @@ int tw_count_pairs_sorted(const void* d_x, const int64_t* d_x_off, const void* d
                           const int64_t* d_z_off, int32_t n_shards, int64_t max_nx,
                           int64_t max_nz, int32_t dtype, int32_t pred, void* d_work,
                           uint64_t* d_out, void* stream);
+/* ---- Variance components (extension; not in the reference, whose only variances are the
+ * closed forms of its Bernoulli model, estimation-experiment/main.py:10-27, :103-104): exact
+ * integer moments of the per-point pair counts of every shard, all shards in one launch with any
+ * mix of sizes (csrc/moments.hip).  With g_ij = 1{x_i > z_j} (TW_PRED_GT) or 2*1{x_i > z_j} +
+ * 1{x_i == z_j} (TW_PRED_HALF), a_i = sum_j g_ij and b_j = sum_i g_ij over shard s,
+ *   d_out[4 s + 0 .. 3] = { S = sum a_i, A2 = sum a_i^2, B2 = sum b_j^2, Q = sum g_ij^2 }
+ * as uint64; S is tw_count_pairs' count.  The caller keeps n (u m)^2 and m (u n)^2 below 2^64
+ * per shard (u = 1 or 2, the predicate's unit).  Layout and arguments as tw_count_pairs; d_work:
+ * device scratch of tw_pair_moments_work_bytes(n_shards, total_nx, total_nz) bytes (total_* =
+ * off[n_shards] - off[0]), read by the sorted algorithm only.  Deterministic (integer sums). */
+int64_t tw_pair_moments_work_bytes(int32_t n_shards, int64_t total_nx, int64_t total_nz);
+int tw_pair_moments(const void* d_x, const int64_t* d_x_off, const void* d_z,
+                    const int64_t* d_z_off, int32_t n_shards, int64_t max_nx, int64_t max_nz,
+                    int32_t dtype, int32_t pred, void* d_work, uint64_t* d_out, void* stream);
+/* The two algorithms of tw_pair_moments, same integers: 1 = all pairs (each lane loops over the
+ * other side), 2 = sorted (both sides sorted in chunks, two binary searches per point and
+ * chunk), 0 = automatic (the default): sorted when max_nx * max_nz >=
+ * TW_MOMENTS_SORTED_MIN_PAIRS.  Process-global A/B hook; results do not depend on it. */
+#define TW_MOMENTS_SORTED_MIN_PAIRS (1 << 17)
+int tw_pair_moments_set_algo(int32_t algo);
+
 /* One step of est.UnNT's loop with the exact sorted count: the counts of tw_count_pairs_sorted
  * for the current partition — except that d_out must already be zero (accumulated into) — and
  * the NEXT repartition: d_x_next / d_z_next = the scores permuted with key_x / key_z (as

@@ -265,6 +265,55 @@ class CompleteCount(BlockSpec):
         return list(counts.astype(np.float64) / pairs.astype(np.float64))
 
 
+class PairMoments(BlockSpec):
+    """Variance-component block: the exact integer moments {S, A2, B2, Q} of the per-point pair
+    counts of est.Un's `X > Z` (E.moments_complete), per block an
+    estimation.VarianceComponents.  tie_mode as CompleteCount's; the wrapping predicates
+    ("subgt", "ne") do not arise from compare_operands and are refused by the engine."""
+
+    def __init__(self, tie_mode: str = "strict"):
+        if tie_mode not in ("strict", "half"):
+            raise ValueError(f"tie_mode must be 'strict' or 'half', not {tie_mode!r}")
+        self.tie_mode = tie_mode
+        self.mode = "half" if tie_mode == "half" else "gt"
+
+    def operands(self, X, Z):
+        x, z, code = E.compare_operands(X, Z)
+        return x, z, code, self.mode
+
+    def work(self, nx, nz, dtype):
+        """both sides are searched (or compared): twice the count's work"""
+        return 2 * E.count_work(nx, nz, self.mode)
+
+    def _components(self, moments, blocks):
+        from .estimation import VarianceComponents
+        unit = 2 if self.mode == "half" else 1
+        return [VarianceComponents(b.nx(), b.nz(), unit, *(int(v) for v in row))
+                for b, row in zip(blocks, moments)]
+
+    def evaluate(self, X, Z, blocks):
+        x, z, code, mode = self.operands(_flat(X), _flat(Z))
+        blocks = _elements(_elements(blocks, "x", _row_size(X)), "z", _row_size(Z))
+        E.moments_check([b.nx() for b in blocks], [b.nz() for b in blocks], mode)
+        xd, zd = L.to_device(x), L.to_device(z)
+        xa, xo = _layout(xd, blocks, "x")
+        za, zo = _layout(zd, blocks, "z")
+        sh = E.Shards(xa, xo, za, zo, code)
+        return self._components(E.moments_complete(sh, mode), blocks)
+
+    def evaluate_device(self, xd, zd, blocks):
+        """evaluate() on float64 or int64 device arrays."""
+        t = L.torch()
+        if xd.dtype != zd.dtype or xd.dtype not in (t.float64, t.int64):
+            raise TypeError("PairMoments.evaluate_device takes two float64 or two int64 tensors")
+        code = L.TW_F64 if xd.dtype == t.float64 else L.TW_I64
+        E.moments_check([b.nx() for b in blocks], [b.nz() for b in blocks], self.mode)
+        xa, xo = _layout(xd, blocks, "x")
+        za, zo = _layout(zd, blocks, "z")
+        sh = E.Shards(xa, xo, za, zo, code)
+        return self._components(E.moments_complete(sh, self.mode), blocks)
+
+
 def _mean_type(X, Z):
     """The type of NumPy's mean of a float kernel's terms: the operands' float type (float32
     stays float32; the device accumulates in float64, so a float32 result is the

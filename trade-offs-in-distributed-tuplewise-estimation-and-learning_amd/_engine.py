@@ -272,6 +272,72 @@ def count_complete(sh: Shards, mode: str = "gt", algo: str = "auto") -> np.ndarr
     return _counts_to_host(run(pred))
 
 
+# tw_pair_moments' "auto": per-launch largest pair count (max_nx * max_nz) from which the sorted
+# moments run; the library holds the same number (TW_MOMENTS_SORTED_MIN_PAIRS, include/
+# tuplewise.h).  From the square-block sweep of tools/time_moments.py on one MI355X
+# (profiles/time_moments.json; us per launch, all pairs / sorted, one block): 128^2 17.2 / 23.4,
+# 256^2 23.0 / 23.5, 512^2 40.7 / 24.0, 1024^2 76 / 25 (64 blocks per launch: the same within
+# 1 us).  All pairs is two launches and grows with the pairs; sorted is three launches
+# (~23 us) and flat up to 1024^2, so the lines cross between 256^2 = 2^16 and 512^2 = 2^18.
+MOMENTS_SORTED_MIN_PAIRS = 1 << 17
+
+_MOMENTS_ALGOS = {"auto": 0, "pairs": 1, "sorted": 2}
+
+
+def moments_check(nx, nz, mode: str) -> None:
+    """Refuse, before any device work, blocks whose sums of squares could leave u64:
+    n (u m)^2 >= 2^64 or m (u n)^2 >= 2^64 (u = 2 in half mode)."""
+    if mode not in ("gt", "half"):
+        raise NotImplementedError(
+            f"pair moments need an ordered predicate ('gt' or 'half'), not {mode!r}: the "
+            f"wrapping predicates are not served")
+    u = 2 if mode == "half" else 1
+    for n, m in zip(np.asarray(nx).reshape(-1).tolist(), np.asarray(nz).reshape(-1).tolist()):
+        if n * (u * m) ** 2 >= 2 ** 64 or m * (u * n) ** 2 >= 2 ** 64:
+            raise ValueError(
+                f"pair moments of a {n} x {m} block (unit {u}) do not fit 64 bits: "
+                f"n (u m)^2 and m (u n)^2 must stay below 2^64")
+
+
+def moments_launch(x_dev, x_off_dev, z_dev, z_off_dev, n, max_nx, max_nz, total_nx, total_nz,
+                   dtype, pred, algo: str = "auto"):
+    """Enqueue the pair moments of all shards (no host sync); returns the (n, 4) int64 device
+    tensor {S, A2, B2, Q} (uint64 semantics).  algo: "auto" leaves the choice to the library
+    (and to its process-global hook); "pairs" / "sorted" set the hook for this call."""
+    if algo not in _MOMENTS_ALGOS:
+        raise ValueError(f"algo must be 'auto', 'pairs' or 'sorted', not {algo!r}")
+    t = L.torch()
+    out = L.empty((n, 4), t.int64)
+    wb = int(L.lib().tw_pair_moments_work_bytes(n, total_nx, total_nz))
+    work = L.empty((max(wb, 8),), t.uint8)
+    if algo != "auto":
+        L.call("tw_pair_moments_set_algo", _MOMENTS_ALGOS[algo])
+    try:
+        L.call("tw_pair_moments", L.ptr(x_dev), L.ptr(x_off_dev), L.ptr(z_dev), L.ptr(z_off_dev),
+               n, max_nx, max_nz, dtype, pred, L.ptr(work), L.ptr(out), L.stream_handle())
+    finally:
+        if algo != "auto":
+            L.call("tw_pair_moments_set_algo", 0)
+    return out
+
+
+def moments_complete(sh: Shards, mode: str = "gt", algo: str = "auto") -> np.ndarray:
+    """Per-shard exact pair moments, an (n_shards, 4) uint64 array {S, A2, B2, Q}: with
+    g_ij = 1{x_i > z_j} ("gt") or 2*1{x_i > z_j} + 1{x_i == z_j} ("half"), a_i = sum_j g_ij and
+    b_j = sum_i g_ij:  S = sum a_i, A2 = sum a_i^2, B2 = sum b_j^2, Q = sum g_ij^2.
+    algo: "pairs" (all pairs), "sorted" (sort + two searches per point), "auto"."""
+    n = sh.n_shards
+    moments_check(sh.nx, sh.nz, mode)
+    if n == 0:
+        return np.zeros((0, 4), dtype=np.uint64)
+    xo, zo = sh.offsets_dev()
+    pred = L.TW_PRED_HALF if mode == "half" else L.TW_PRED_GT
+    out = moments_launch(sh.x, xo, sh.z, zo, n, int(sh.nx.max()), int(sh.nz.max()),
+                         int(sh.x_off[-1] - sh.x_off[0]), int(sh.z_off[-1] - sh.z_off[0]),
+                         sh.dtype, pred, algo)
+    return _counts_to_host(out)
+
+
 _I32_LIMIT = 2 ** 31  # arrays up to this many elements take int32 pair indices
 
 

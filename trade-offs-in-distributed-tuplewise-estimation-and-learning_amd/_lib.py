@@ -65,6 +65,9 @@ _SIGNATURES = {
     "tw_count_pairs_sorted_work_bytes": [_i32, _i64],
     "tw_count_sorted_set_chunk": [_i64],
     "tw_count_pairs_sorted": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
+    "tw_pair_moments_work_bytes": [_i32, _i64, _i64],
+    "tw_pair_moments": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
+    "tw_pair_moments_set_algo": [_i32],
     "tw_count_pairs_idx": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp],
     "tw_count_idx_set_parts": [_i32],
     "tw_count_idx_set_variant": [_i32],
@@ -234,6 +237,7 @@ _SIGNATURES = {
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
     "tw_count_pairs_sorted_work_bytes": ctypes.c_int64,
+    "tw_pair_moments_work_bytes": ctypes.c_int64,
     "tw_rank_images_work_bytes": ctypes.c_int64,
     "tw_peer_buffer_bytes": ctypes.c_int64,
     "tw_count_pairs_rng_work_bytes": ctypes.c_int64,

@@ -160,6 +160,13 @@ class HipOps:
         return E.count_launch(x, x_off_dev, z, z_off_dev, int(n_shards), int(max_nx),
                               int(max_nz), int(dtype), int(pred), algo)
 
+    def moments(self, x, x_off_dev, z, z_off_dev, n_shards, max_nx, max_nz, total_nx, total_nz,
+                dtype, pred, algo="auto"):
+        """The (n_shards, 4) pair moments {S, A2, B2, Q} of every shard (tw_pair_moments)."""
+        return E.moments_launch(x, x_off_dev, z, z_off_dev, int(n_shards), int(max_nx),
+                                int(max_nz), int(total_nx), int(total_nz), int(dtype),
+                                int(pred), algo)
+
     def count_step(self, x, x_off_dev, z, z_off_dev, n_shards, max_nx, max_nz, dtype, pred,
                    out, x_next, key_x, z_next, key_z, out_next):
         """Counts of the current partition into `out` (already zero) and, in the same launch,
@@ -761,6 +768,42 @@ class ShardedSample:
             return out[0]
         return self.ops.count(self.X, self.x_off_dev, self.Z, self.z_off_dev, self.N,
                               self.max_nx, self.max_nz, self.dtype, self.pred, algo=self.algo)
+
+    def _moments_ops(self, what):
+        """The ops' moments kernel, for one process's resident sample (multi-rank moments are
+        not built: the per-point counts of a shard would have to cross ranks)."""
+        if self.G > 1:
+            raise NotImplementedError(f"ShardedSample.{what}: several ranks are not served")
+        f = getattr(self.ops, "moments", None)
+        if f is None:
+            raise NotImplementedError(
+                f"ShardedSample.{what}: these ops have no pair-moments kernel")
+        return f
+
+    def local_moments(self):
+        """Per-local-shard exact pair moments {S, A2, B2, Q} of the current layout: an (N, 4)
+        int64 device tensor with uint64 semantics (S is local_counts()' count; see
+        estimation.VarianceComponents).  World size 1 only."""
+        f = self._moments_ops("local_moments")
+        mode = "half" if self.pred == L.TW_PRED_HALF else "gt"
+        E.moments_check(np.diff(self.x_off), np.diff(self.z_off), mode)
+        return f(self.X, self.x_off_dev, self.Z, self.z_off_dev, self.N, self.max_nx,
+                 self.max_nz, int(self.x_off[-1] - self.x_off[0]),
+                 int(self.z_off[-1] - self.z_off[0]), self.dtype, self.pred)
+
+    def Un_var(self):
+        """The whole resident sample as ONE block: its estimation.VarianceComponents (what
+        est.Un_var gives on the same scores, in this sample's tie mode).  World size 1 only."""
+        from .estimation import VarianceComponents
+        f = self._moments_ops("Un_var")
+        mode = "half" if self.pred == L.TW_PRED_HALF else "gt"
+        n, m = int(self.n_loc), int(self.m_loc)
+        E.moments_check([n], [m], mode)
+        xo = self.ops.to_dev(np.array([0, n], dtype=np.int64))
+        zo = self.ops.to_dev(np.array([0, m], dtype=np.int64))
+        out = f(self.X, xo, self.Z, zo, 1, n, m, n, m, self.dtype, self.pred)
+        row = np.asarray(out.cpu().numpy()).view(np.uint64)[0]
+        return VarianceComponents(n, m, 2 if mode == "half" else 1, *(int(v) for v in row))
 
     def _oneshot_rank_ok(self) -> bool:
         """One-shot counts on rank images: the step-chain predicates, a device sample of fewer

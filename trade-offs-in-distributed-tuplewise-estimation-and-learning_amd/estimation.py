@@ -96,6 +96,170 @@ def UnNT(X, Z, N, T, sampling_type, tie_mode="strict"):
                     for _ in range(T)])
 
 
+class VarianceComponents:
+    """The exact integer moments of one block's per-point pair counts, and what follows from
+    them (extension: the reference has only the closed forms above, for its Bernoulli model).
+
+    n, m: the block's sizes; unit: 1 ("strict", g_ij = 1{x_i > z_j}) or 2 ("half", g_ij =
+    2*1{x_i > z_j} + 1{x_i == z_j}); with a_i = sum_j g_ij and b_j = sum_i g_ij,
+    S = sum a_i, A2 = sum a_i^2, B2 = sum b_j^2, Q = sum g_ij^2, all Python ints.
+
+    theta, s10, s01 and vh are each one exact rational rounded once to float64; s10 and s01 are
+    DeLong's components (the ddof = 1 sample variances of a_i / (u m) and b_j / (u n)), vh the
+    plain variance of the kernel.  sigma_0/1/2 solve E[s10] = sigma_1 + sigma_0 / m,
+    E[s01] = sigma_2 + sigma_0 / n in Var_Un's parametrisation (method of moments), in float64.
+    n < 2 or m < 2 gives NaN components (theta stays exact); an empty block gives zeros."""
+
+    __slots__ = ("n", "m", "unit", "S", "A2", "B2", "Q")
+
+    def __init__(self, n, m, unit, S, A2, B2, Q):
+        if unit not in (1, 2):
+            raise ValueError("unit must be 1 (strict) or 2 (half)")
+        for k, v in zip(self.__slots__, (n, m, unit, S, A2, B2, Q)):
+            object.__setattr__(self, k, int(v))
+
+    def __setattr__(self, k, v):
+        raise AttributeError("VarianceComponents is immutable")
+
+    __delattr__ = __setattr__
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, VarianceComponents) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "VarianceComponents(" + ", ".join(
+            f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+
+    @staticmethod
+    def _ratio(num: int, den: int) -> float:
+        from fractions import Fraction
+        return float(Fraction(num, den))
+
+    @property
+    def _empty(self) -> bool:
+        return self.n * self.m == 0
+
+    @property
+    def theta(self) -> float:
+        if self._empty:
+            return 0.0
+        return self._ratio(self.S, self.unit * self.n * self.m)
+
+    @property
+    def s10(self) -> float:
+        n, m, u = self.n, self.m, self.unit
+        if self._empty:
+            return 0.0
+        if n < 2:
+            return float("nan")
+        return self._ratio(n * self.A2 - self.S ** 2, u * u * m * m * n * (n - 1))
+
+    @property
+    def s01(self) -> float:
+        n, m, u = self.n, self.m, self.unit
+        if self._empty:
+            return 0.0
+        if m < 2:
+            return float("nan")
+        return self._ratio(m * self.B2 - self.S ** 2, u * u * n * n * m * (m - 1))
+
+    @property
+    def vh(self) -> float:
+        n, m, u = self.n, self.m, self.unit
+        if self._empty:
+            return 0.0
+        return self._ratio(n * m * self.Q - self.S ** 2, u * u * n * n * m * m)
+
+    @property
+    def sigma_0(self) -> float:
+        if self._empty:
+            return 0.0
+        if self.n < 2 or self.m < 2:
+            return float("nan")
+        return (self.vh - self.s10 - self.s01) / (1 - 1 / self.n - 1 / self.m)
+
+    @property
+    def sigma_1(self) -> float:
+        return 0.0 if self._empty else self.s10 - self.sigma_0 / self.m
+
+    @property
+    def sigma_2(self) -> float:
+        return 0.0 if self._empty else self.s01 - self.sigma_0 / self.n
+
+    @property
+    def var_delong(self) -> float:
+        return 0.0 if self._empty else self.s10 / self.n + self.s01 / self.m
+
+    @property
+    def var_Un(self) -> float:
+        if self._empty:
+            return 0.0
+        n, m = self.n, self.m
+        return self.sigma_1 / n + self.sigma_2 / m + self.sigma_0 / (n * m)
+
+    def var_UnN(self, N) -> float:
+        """Variance of the block-wise estimator over N shards of this sample."""
+        if self._empty:
+            return 0.0
+        return self.var_Un + (N - 1) * self.sigma_0 / (self.n * self.m)
+
+    def var_UnNT(self, N, T) -> float:
+        """Variance of the average of T repartitioned block-wise estimators."""
+        if self._empty:
+            return 0.0
+        return self.var_Un + (N - 1) * self.sigma_0 / (self.n * self.m * T)
+
+
+_MOMENTS = {"strict": Bk.PairMoments("strict"), "half": Bk.PairMoments("half")}
+
+
+def _moments_spec(tie_mode):
+    if tie_mode not in _MOMENTS:
+        raise ValueError(f"tie_mode must be 'strict' or 'half', not {tie_mode!r}")
+    return _MOMENTS[tie_mode]
+
+
+def Un_var(X, Z, tie_mode="strict") -> VarianceComponents:
+    """The variance components of Un(X, Z, tie_mode) from the sample itself: one block, host
+    arrays of any dtype Un takes.  `.theta` has the bits of Un(X, Z, tie_mode); `.var_Un`,
+    `.var_delong`, `.var_UnN(N)` and `.var_UnNT(N, T)` estimate the variances."""
+    X = np.asarray(X)
+    Z = np.asarray(Z)
+    return _moments_spec(tie_mode).evaluate(X, Z, [Bk.whole(X, Z)])[0]
+
+
+def UnN_var(X, Z, N, sampling_type, tie_mode="strict"):
+    """UnN(X, Z, N, sampling_type, tie_mode) with a variance estimate: (value, var, blocks).
+
+    Makes exactly UnN's in-place shuffles and RNG draws (plan_un), so the caller's arrays and
+    np.random end where UnN leaves them and `value` is bit-identical to UnN's from the same
+    state.  blocks: the VarianceComponents of every evaluated block, in order.  var: the sum
+    of the blocks' var_Un divided by the square of the number of block values that enter the
+    mean (a degenerate SWOR block enters as value 0 with variance 0).  This treats the blocks
+    as independent samples: it leaves out the (negative) covariance that cutting one finite
+    sample without replacement induces between its blocks.  "prop-SWR" blocks overlap and are
+    not served."""
+    if sampling_type == "prop-SWR":
+        raise NotImplementedError(
+            "UnN_var: prop-SWR blocks resample the same scores; their variances do not add")
+    spec = _moments_spec(tie_mode)
+    plan = Bk.plan_un(X, Z, N, spec, sampling_type, "est")
+    blocks = [p[1] for p in plan if p[0] == "val"]
+    comps = spec.evaluate(X, Z, blocks) if blocks else []
+    # (a block the cuts left empty on one side is 0 / 0 = NaN in UnN's mean, and so here)
+    value = Bk.finish_un(plan, [np.float64(c.theta) if c.n * c.m else np.float64("nan")
+                                for c in comps])
+    k = len(plan)
+    var = float(sum(c.var_Un for c in comps)) / (k * k) if k else float("nan")
+    return value, var, comps
+
+
 def replicate(estimator, gen_X, gen_Z, n_tries, *args, flush_elems=1 << 24, **kwargs):
     """``[estimator(gen_X(), gen_Z(), *args, **kwargs) for _ in range(n_tries)]`` — the
     Monte-Carlo loops of main.py:106-112 — with identical results and identical NumPy RNG
