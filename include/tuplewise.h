@@ -1079,6 +1079,34 @@ int tw_np_randint_dev(uint32_t* key, int32_t* pos, const uint32_t* d_table, int3
                       int32_t* d_out, int64_t out_len, void* d_work, int64_t* progress,
                       void* stream);
 
+/* ---- One-sample pairwise U-statistics (csrc/selfpairs.hip; tuplewise.onesample; DESIGN.md
+ * §4.9; an extension, not in the reference).  Pairs i < j of ONE sample, per shard:
+ *   TW_SELF_GINI     sum |s_i - s_j|                          one double
+ *   TW_SELF_VAR      sum (s_i - s_j)^2 / 2                    one double
+ *   TW_SELF_KENDALL  items (a, b) of two 8-byte values; five uint64 C, D, Tx, Ty, Txy:
+ *                    C = #{(a_i>a_j & b_i>b_j) | (a_i<a_j & b_i<b_j)}, D = the two mixed cases,
+ *                    Tx = #{a_i==a_j}, Ty = #{b_i==b_j}, Txy = #{both} — plain comparisons of
+ *                    the raw values (NaN compares false, -0.0 == 0.0; TW_I64 as int64).
+ * d_off[n_shards + 1] counts items; shards of any mix of sizes run in one launch, a shard of
+ * fewer than 2 items gives zeros.  The float kernels take TW_F64 only.  tw_self_pairs walks the
+ * triangle of tile pairs (tw_self_pairs_tile() points per tile edge), each unordered pair once;
+ * tw_self_pairs_idx32 evaluates pairs (d_i[p], d_j[p]), absolute item positions, for p in
+ * [d_pair_off[s], d_pair_off[s + 1]).  Results do not depend on scheduling: block partials go
+ * through d_work (tw_self_pairs_work_bytes / tw_self_pairs_idx_work_bytes bytes) and are added
+ * in a fixed order.  Argument errors (n_shards < 0, a negative size, an unknown kern or dtype,
+ * a float kern with TW_I64) return TW_ERR_ARG before any device work. */
+#define TW_SELF_GINI 0
+#define TW_SELF_VAR 1
+#define TW_SELF_KENDALL 2
+int64_t tw_self_pairs_work_bytes(int32_t n_shards, int64_t max_n);
+int64_t tw_self_pairs_idx_work_bytes(int32_t n_shards, int64_t max_pairs);
+int32_t tw_self_pairs_tile(void);
+int tw_self_pairs(const void* d_s, const int64_t* d_off, int32_t n_shards, int64_t max_n,
+                  int32_t dtype, int32_t kern, void* d_work, void* d_out, void* stream);
+int tw_self_pairs_idx32(const void* d_s, const int32_t* d_i, const int32_t* d_j,
+                        const int64_t* d_pair_off, int32_t n_shards, int64_t max_pairs,
+                        int32_t dtype, int32_t kern, void* d_work, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

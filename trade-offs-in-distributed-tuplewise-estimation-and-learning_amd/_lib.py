@@ -23,6 +23,7 @@ TW_F64, TW_I64 = 0, 1
 TW_PRED_GT, TW_PRED_HALF, TW_PRED_SUBGT = 0, 1, 2
 TW_KERN_PROD, TW_KERN_GINI, TW_KERN_HINGE, TW_KERN_LOGISTIC = 0, 1, 2, 3
 TW_LOSS_HINGE, TW_LOSS_LOGISTIC = 0, 1
+TW_SELF_GINI, TW_SELF_VAR, TW_SELF_KENDALL = 0, 1, 2
 
 _vp, _i64, _i32, _u64, _f64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                ctypes.c_uint64, ctypes.c_double)
@@ -233,6 +234,11 @@ _SIGNATURES = {
     "tw_np_randint_dev_work_bytes": [_i32, _i32, _i32, _i32],
     "tw_np_randint_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                           _vp, _i64, _vp, _vp, _vp],
+    "tw_self_pairs_work_bytes": [_i32, _i64],
+    "tw_self_pairs_idx_work_bytes": [_i32, _i64],
+    "tw_self_pairs_tile": [],
+    "tw_self_pairs": [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp],
+    "tw_self_pairs_idx32": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -250,6 +256,8 @@ _RESTYPES = {
     "tw_eval_small_work": ctypes.c_int64,
     "tw_words_checksum_acc_words": ctypes.c_int64,
     "tw_np_randint_dev_work_bytes": ctypes.c_int64,
+    "tw_self_pairs_work_bytes": ctypes.c_int64,
+    "tw_self_pairs_idx_work_bytes": ctypes.c_int64,
 }
 
 _lib = None
