@@ -209,6 +209,22 @@ int tw_count_pairs_chain_bound(const void* d_x_bag, const int64_t* d_x_off, int6
                                int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
                                int32_t half, int64_t image_bound, uint64_t* d_out,
                                void* stream);
+/* tw_count_pairs_chain_bound whose bit-sliced count reads bit planes built ONCE per bag
+ * (DESIGN §4.1f): a pre-pass (k_chain_planes) writes the planes of every bag's x groups (and
+ * of its z groups, where the x remainder is counted with the roles swapped) into d_work, and
+ * the count (k_count_chain_planes) follows on the same stream inside this call.  d_work:
+ * at least tw_chain_planes_work_bytes(...) bytes (else TW_ERR_ARG before any launch), written
+ * and read only inside the call — calls on different streams must not share it.  Same counts,
+ * same packed-kernel cases (half = 1, a bound of 2^24 or more, tiny bags) as the _bound form. */
+int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
+                                const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
+                                int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
+                                int32_t half, int64_t image_bound, uint64_t* d_out,
+                                void* stream, void* d_work, int64_t work_bytes);
+/* Bytes of d_work for tw_count_pairs_chain_planes / tw_chain_unpack_count_planes on steps x
+ * n_shards bags of at most max_nx x max_nz images (0 where the count runs packed). */
+int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
+                                   int64_t max_nz, int32_t half, int64_t image_bound);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
  * estimation-experiment/main.py:29-31's integer): each bag's z images (integers in
  * [0, z_total], z_total = the Z count the images were ranked against) counting-sorted into
@@ -223,11 +239,16 @@ int tw_count_pairs_chain_bucket(const void* d_x_bag, const int64_t* d_x_off, int
  * round (1 or 16 / elements per thread); 0 = automatic.  Process-global; results do not depend
  * on it (the order inside a bag does). */
 int tw_chain_set_emit(int32_t epr, int32_t steps_per_round);
-/* Tuning hook for tw_count_pairs_chain and tw_count_pairs_chain_bound: R = 8 or 16 x-images per
- * lane forces the packed kernel, R = 2 or 4 plane groups per lane the bit-sliced one (where
+/* Tuning hook for tw_count_pairs_chain and its _bound / _planes forms: R = 8 or 16 x-images per
+ * lane forces the packed kernel, R = 2, 3 or 4 plane groups per lane (3: the _planes form; the
+ * _bound form takes it as 4) the bit-sliced one (where
  * the call allows it: a bound below 2^24, strict predicate), 0 = automatic; z-chunk length
  * for either kernel (0 = automatic).  Process-global; results do not depend on it. */
 int tw_count_chain_set_plan(int32_t R, int64_t z_chunk);
+/* A/B hook for tw_count_pairs_chain_planes: 0 counts every x remainder as a padded plane group
+ * (no swapped items), 2 swaps wherever chainplan.h's per-bag rule allows, 1 (default) does so
+ * in launches large enough to gain from it.  Process-global; same counts. */
+int tw_count_chain_set_swap(int32_t swap);
 /* The scores in their final order after the chains (one process): d_x_out[d_x_pos[e]] =
  * d_x[e] (8-B values), likewise for Z. */
 int tw_chain_scatter(const void* d_x, const uint32_t* d_x_pos, int64_t n_x, const void* d_z,
@@ -947,6 +968,16 @@ int tw_chain_unpack_count_bound(const uint64_t* d_recv, int32_t world, int32_t s
                                 uint32_t* d_cursors, int32_t* d_flag, const int64_t* d_x_off,
                                 const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
                                 int64_t image_bound, uint64_t* d_out, void* stream);
+/* tw_chain_unpack_count whose count is tw_count_pairs_chain_planes' (d_work, work_bytes: its
+ * workspace, for bag strides n_x / n_z). */
+int tw_chain_unpack_count_planes(const uint64_t* d_recv, int32_t world, int32_t steps,
+                                 int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
+                                 int64_t x_shard, int64_t z_shard, int32_t n_shards,
+                                 void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
+                                 int32_t* d_flag, const int64_t* d_x_off,
+                                 const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
+                                 int64_t image_bound, uint64_t* d_out, void* stream,
+                                 void* d_work, int64_t work_bytes);
 /* The incomplete statistic on the step chains over ranks (cs.UnNBT, compute_stats.py:119-123,
  * with device-RNG draws): tw_chain_unpack_exact writes every received record {image, local
  * position} of a chunk's (source, step) buckets (tw_chain_emit's exchange layout, strict

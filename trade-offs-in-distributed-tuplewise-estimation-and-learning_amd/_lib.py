@@ -58,9 +58,13 @@ _SIGNATURES = {
                              _vp],
     "tw_count_pairs_chain_bound": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32,
                                    _i64, _vp, _vp],
+    "tw_count_pairs_chain_planes": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32,
+                                    _i64, _vp, _vp, _vp, _i64],
+    "tw_chain_planes_work_bytes": [_i32, _i32, _i64, _i64, _i32, _i64],
     "tw_count_pairs_chain_bucket": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64,
                                     _i32, _vp, _vp],
     "tw_count_chain_set_plan": [_i32, _i64],
+    "tw_count_chain_set_swap": [_i32],
     "tw_chain_set_emit": [_i32, _i32],
     "tw_chain_scatter": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp],
     "tw_count_pairs_sorted_work_bytes": [_i32, _i64],
@@ -210,6 +214,9 @@ _SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "tw_chain_unpack_count_bound": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    "tw_chain_unpack_count_planes": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
+                                     _vp, _i64],
     "tw_chain_unpack_exact": [_vp, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "tw_count_pairs_chain_rng": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64,
                                  _u64, _u64, _vp, _vp],
@@ -258,6 +265,7 @@ _RESTYPES = {
     "tw_np_randint_dev_work_bytes": ctypes.c_int64,
     "tw_self_pairs_work_bytes": ctypes.c_int64,
     "tw_self_pairs_idx_work_bytes": ctypes.c_int64,
+    "tw_chain_planes_work_bytes": ctypes.c_int64,
 }
 
 _lib = None

@@ -107,6 +107,38 @@ __device__ __forceinline__ int64_t bits_uniform(int64_t v) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
+// The scalar-side loop of a wave item: n wave-uniform images against the lane's R groups of NB
+// planes.  load(j) gives lane l the image j + l, complemented z or plain x (0 past the end); the
+// images go 64 at a time through one VGPR, the next 64 in flight, and reach the scalar side by
+// v_readlane_b32: one extra VALU instruction per image and wave.
+template <int NB, int R, class Load>
+__device__ __forceinline__ void bits_scalar_loop(const uint32_t (&pl)[R][NB], uint32_t (&acc)[R],
+                                                 int n, Load load) {
+  uint32_t next = load(0);
+  for (int j = 0; j < n; j += 64) {
+    const uint32_t sv = next;
+    next = load(j + 64);
+    const int cnt = min(64, n - j);
+    for (int l = 0; l < cnt; l += 2) {  // an odd last image pairs with a padded slot: 0
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const uint32_t sc = (uint32_t)__builtin_amdgcn_readlane((int)sv, l + u);
+        uint32_t m[NB], c[R];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) m[b] = bits_mask(sc, b);
+#pragma unroll
+        for (int r = 0; r < R; ++r) c[r] = pl[r][0] & m[0];
+#pragma unroll
+        for (int b = 1; b < NB; ++b)
+#pragma unroll
+          for (int r = 0; r < R; ++r) c[r] = bits_carry(pl[r][b], m[b], c[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = bits_popc_add(c[r], acc[r]);
+      }
+    }
+  }
+}
+
 // One wave item: 64 * 32 * R x images [x0, min(x0 + 64 * 32 * R, xe)) of a bag (R plane groups
 // per lane; group r, bit k of a lane is image x0 + (32 r + k) * 64 + lane; slots past xe hold 0)
 // against its z images [z0, z1).  z goes 64 at a time through one VGPR (coalesced load,
@@ -149,29 +181,36 @@ __device__ __forceinline__ unsigned long long bits_count_item(const float* __res
     const uint32_t v = bits_z_image(zp[min(j + lane, nz - 1)]);  // (no branch around the load)
     return j + lane < nz ? v : kBitsZNever;
   };
-  uint32_t znext = z_load(0);
-  for (int j = 0; j < nz; j += 64) {
-    const uint32_t zv = znext;
-    znext = z_load(j + 64);
-    const int cnt = min(64, nz - j);
-    for (int l = 0; l < cnt; l += 2) {  // an odd last z pairs with a padded slot (counts nothing)
+  bits_scalar_loop<NB, R>(pl, acc, nz, z_load);
+  unsigned long long tot = 0;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const uint32_t zc = (uint32_t)__builtin_amdgcn_readlane((int)zv, l + u);
-        uint32_t m[NB], c[R];
+  for (int r = 0; r < R; ++r) tot += acc[r];
+  return tot;
+}
+
+// One wave item on planes built beforehand (chainplan.h; chain.hip's k_chain_planes): R groups
+// of NB plane words per lane at pw (group r, plane b: pw[(r * NB + b) * 64 + lane]) against
+// the ns scalar-side images at sf — a z chunk (stored negated; complemented here), or, with
+// the roles SWAPPED, x images against complemented z planes: the carry out of x + ~z does not
+// care which operand is the lane's.  The scalar loop is bits_count_item's; padded scalar
+// slots hold 0 in either role (a complemented z that is never less, an x that is never more).
+template <int NB, int R>
+__device__ __forceinline__ unsigned long long bits_count_planes(const uint32_t* __restrict__ pw,
+                                                                const float* __restrict__ sf,
+                                                                int ns, bool swapped, int lane) {
+  uint32_t pl[R][NB], acc[R];
 #pragma unroll
-        for (int b = 0; b < NB; ++b) m[b] = bits_mask(zc, b);
+  for (int r = 0; r < R; ++r) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) c[r] = pl[r][0] & m[0];
-#pragma unroll
-        for (int b = 1; b < NB; ++b)
-#pragma unroll
-          for (int r = 0; r < R; ++r) c[r] = bits_carry(pl[r][b], m[b], c[r]);
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = bits_popc_add(c[r], acc[r]);
-      }
-    }
+    for (int b = 0; b < NB; ++b) pl[r][b] = pw[(r * NB + b) * 64 + lane];
+    acc[r] = 0;
   }
+  auto s_load = [&](int j) -> uint32_t {
+    const float f = sf[min(j + lane, ns - 1)];  // (no branch around the load)
+    const uint32_t v = swapped ? bits_x_image(f) : bits_z_image(f);
+    return j + lane < ns ? v : 0u;
+  };
+  bits_scalar_loop<NB, R>(pl, acc, ns, s_load);
   unsigned long long tot = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) tot += acc[r];

@@ -32,6 +32,7 @@
 // (tw_rank_images_query with half = 1), and ONE clamped packed add gives [x > z] and [x >= z]
 // for a z: clamp(h(x) - g(z)) == 1 <=> x >= z.  Half units = the sum of both lanes.
 #include "bitcount.h"
+#include "chainplan.h"
 #include "feistel.h"
 #include "pkcount.h"
 #include "records.h"
@@ -448,6 +449,34 @@ __device__ __forceinline__ unsigned long long count_chain_item(const void* __res
   return wave_sum_u64(tot);
 }
 
+// The count's epilogue: the block's wave totals, one u64 atomic per block and bag (v: the
+// wave's bag; active: it counted one).
+__device__ __forceinline__ void count_chain_epilogue(unsigned long long tot, bool active, int v,
+                                                     int wid, int lane,
+                                                     unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long part[kBlock / kWave];
+  __shared__ int part_v[kBlock / kWave];
+  if (lane == 0) {
+    part[wid] = tot;
+    part_v[wid] = active ? v : -1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int cur = part_v[0];
+    unsigned long long sum = part[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / kWave; ++w) {
+      if (part_v[w] != cur) {
+        if (cur >= 0 && sum) atomicAdd(out + cur, sum);
+        cur = part_v[w];
+        sum = 0;
+      }
+      sum += part[w];
+    }
+    if (cur >= 0 && sum) atomicAdd(out + cur, sum);
+  }
+}
+
 // Work items as k_count_rank (csrc/rankimage.hip): per wave (bag v = step * N + shard, x tile,
 // z chunk), shard-major logical order dealt to the XCDs in contiguous ranges, one u64 atomic
 // per block and bag.  TILE: x images per item; item(x0, xe, z0, z1, lane) -> the lane's count.
@@ -482,27 +511,7 @@ __device__ __forceinline__ void count_chain_block(const int64_t* __restrict__ x_
   }
   unsigned long long tot = 0;
   if (active) tot = item_count(x0, xe, z0, z1, lane);
-  __shared__ unsigned long long part[kBlock / kWave];
-  __shared__ int part_v[kBlock / kWave];
-  if (lane == 0) {
-    part[wid] = tot;
-    part_v[wid] = active ? v : -1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int cur = part_v[0];
-    unsigned long long sum = part[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / kWave; ++w) {
-      if (part_v[w] != cur) {
-        if (cur >= 0 && sum) atomicAdd(out + cur, sum);
-        cur = part_v[w];
-        sum = 0;
-      }
-      sum += part[w];
-    }
-    if (cur >= 0 && sum) atomicAdd(out + cur, sum);
-  }
+  count_chain_epilogue(tot, active, v, wid, lane, out);
 }
 
 template <int R, bool HALF>
@@ -541,6 +550,101 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_bits(
       [&](int64_t x0, int64_t xe, int64_t z0, int64_t z1, int lane) {
         return count_chain_item_bits<NB, R>(xb, x0, xe, zb, z0, z1, lane);
       });
+}
+
+// The bit-sliced count on planes built once per bag (chainplan.h).
+// k_count_chain_bits transposes an x tile in every one of the bag's z chunks (16 times at the
+// bench shape) and pads the x tail to a whole group.  Here a pre-pass makes the planes once:
+// one wave per (bag, group of 2048 images, side) loads the group's 32 images per lane (bit k
+// of lane l: image g * 2048 + k * 64 + l), converts them (x: bits_x_image; z: complemented,
+// bits_z_image), transposes and stores NB planes of 64 u32 — one 256-B store each.  Slots past
+// the bag's end hold 0 on either side (z: kBitsZNever), so they count nothing in either role.
+// Only the groups the bag's items read are written: its full x groups (and a padded last one
+// where the remainder is not swapped), its z groups where it is.
+template <int NB>
+__global__ __launch_bounds__(kBlock) void k_chain_planes(
+    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int gx, int gz, int swap, uint32_t* __restrict__ work) {
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  int64_t w = (int64_t)blockIdx.x * (kBlock / kWave) + wid;
+  const int64_t x_waves = (int64_t)n_bags * gx;
+  const bool zside = w >= x_waves;
+  const int G = zside ? gz : gx;
+  if (zside) w -= x_waves;
+  if (G == 0 || w >= (int64_t)n_bags * G) return;
+  const int v = (int)(w / G), g = (int)(w - (int64_t)v * G);
+  const int c = v / n_shards, s = v - c * n_shards;
+  const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
+  const PlanesBag bag = planes_bag(nx, nz, swap != 0);
+  if (g >= (zside ? bag.zgroups : bag.xgroups)) return;
+  const float* __restrict__ src =
+      zside ? zb + bits_uniform((int64_t)c * z_stride + z_off[s] + (int64_t)g * kPlaneGroup)
+            : xb + bits_uniform((int64_t)c * x_stride + x_off[s] + (int64_t)g * kPlaneGroup);
+  const int cnt =  // >= 1
+      __builtin_amdgcn_readfirstlane((int)min((int64_t)kPlaneGroup,
+                                              (zside ? nz : nx) - (int64_t)g * kPlaneGroup));
+  float raw[32];
+  uint32_t a[32];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) raw[k] = src[min(k * 64 + lane, cnt - 1)];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    const uint32_t img = zside ? bits_z_image(raw[k]) : bits_x_image(raw[k]);
+    a[k] = k * 64 + lane < cnt ? img : (zside ? kBitsZNever : 0u);
+  }
+  bits_transpose32(a);
+  uint32_t* __restrict__ dst =
+      work + bits_uniform(planes_word(NB, (zside ? x_waves : 0) + w, 0, 0));
+#pragma unroll
+  for (int b = 0; b < NB; ++b) dst[b * 64 + lane] = a[b];
+}
+
+// The count on those planes: work items of chainplan.h (a plane item: up to p.R x groups
+// against a z chunk; a swapped item: an x-remainder chunk against up to p.R z groups) in
+// count_chain_block's XCD order and with its epilogue.  The groups of an item are
+// wave-uniform, so it runs the instantiation for exactly that many: no group tests in the loop.
+template <int NB>
+__global__ __launch_bounds__(kBlock) void k_count_chain_planes(
+    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, PlanesPlan p, const uint32_t* __restrict__ work,
+    unsigned long long* __restrict__ out) {
+  const int lb = xcd_block(blockIdx.x, gridDim.x);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int item = lb * (kBlock / kWave) + wid;
+  const int v = item / p.per_bag;
+  bool active = v < n_bags;
+  unsigned long long tot = 0;
+  if (active) {
+    const int c = v / n_shards, s = v - c * n_shards;
+    const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
+    const PlanesItem it = planes_item(p, nx, nz, item - v * p.per_bag);
+    active = it.active;
+    if (active) {
+      const int64_t group = it.swapped ? (int64_t)n_bags * p.gx + (int64_t)v * p.gz + it.g0
+                                       : (int64_t)v * p.gx + it.g0;
+      const uint32_t* __restrict__ pw = work + bits_uniform(planes_word(NB, group, 0, 0));
+      const float* __restrict__ sf =
+          it.swapped ? xb + bits_uniform((int64_t)c * x_stride + x_off[s] + it.s0)
+                     : zb + bits_uniform((int64_t)c * z_stride + z_off[s] + it.s0);
+      const int ns = __builtin_amdgcn_readfirstlane((int)(it.s1 - it.s0));
+      const int ng = __builtin_amdgcn_readfirstlane(it.ng);
+      unsigned long long t;
+      if (ng == 4)
+        t = bits_count_planes<NB, 4>(pw, sf, ns, it.swapped, lane);
+      else if (ng == 3)
+        t = bits_count_planes<NB, 3>(pw, sf, ns, it.swapped, lane);
+      else if (ng == 2)
+        t = bits_count_planes<NB, 2>(pw, sf, ns, it.swapped, lane);
+      else
+        t = bits_count_planes<NB, 1>(pw, sf, ns, it.swapped, lane);
+      tot = wave_sum_u64(t);
+    }
+  }
+  count_chain_epilogue(tot, active, v, wid, lane, out);
 }
 
 // ------------------------------------------- the call's final arrays over ranks: one exchange
@@ -683,6 +787,7 @@ struct ChainPlan {
 };
 static int g_chain_R = 0;  // tuning hooks (tw_count_chain_set_plan); 0 = automatic
 static int64_t g_chain_zchunk = 0;
+static int g_planes_swap = 1;  // (tw_count_chain_set_swap: 0 never, 1 automatic, 2 always)
 
 // strict: R in {16, 8} x-images per lane, least padded slots (ties to 16); half: R = 8 {g, h}
 // pairs (the same 8 packed registers per lane).  z chunks: as many as give ~150 work items per
@@ -707,6 +812,9 @@ constexpr int64_t kChainMinZ = 600;
 // the packed kernel (profiles/r07_count_bits_ab.json): headline K = 20 8.48 -> 5.77 ms,
 // K = 32 13.26 -> 9.07, K = 4 1.79 -> 1.19; per-rank shapes G = 2 / 4 / 8 at K = 20 0.66-0.67
 // of the packed time, C2 (one 1e5 x 1e5 bag, R = 2) 0.294 -> 0.260; none slower.
+// (The _planes entries keep this function's choice between the packed and the bit-sliced
+// count — kBitsMaxPad included — and then plan their own items: chainplan.h's planes_plan,
+// whose items have no transposes to amortise and are much shorter.)
 constexpr int64_t kBitsItems = 256 * 4 * 40;
 constexpr int64_t kBitsMinZ = 1024;
 constexpr double kBitsMaxPad = 1.25;
@@ -730,8 +838,9 @@ static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool
       const bool few = ceil_div(max_nx, (int64_t)kWave * 32 * 4) * n_bags *
                            ceil_div(max_nz, kBitsMinZ) < 256 * 4 * 2;
       const int tieR = few ? 2 : 4;
+      const int forceR = g_chain_R == 3 ? 4 : g_chain_R;  // (3: k_count_chain_planes only)
       for (int R : {tieR, 6 - tieR}) {
-        if (g_chain_R && R != g_chain_R) continue;
+        if (forceR && R != forceR) continue;
         const int64_t slots = ceil_div(max_nx, (int64_t)kWave * 32 * R) * kWave * 32 * R;
         if (bbest < 0 || slots < bbest) {
           bbest = slots;
@@ -1014,6 +1123,12 @@ static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64
                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
                               int32_t half, int64_t image_bound, uint64_t* d_out,
                               hipStream_t st);
+// ... and of the _planes entries (d_work: their plane workspace)
+static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
+                                   const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
+                                   int32_t n_shards, int32_t steps, int64_t max_nx,
+                                   int64_t max_nz, int32_t half, int64_t image_bound,
+                                   uint64_t* d_out, void* d_work, hipStream_t st);
 }  // namespace tw
 
 static int count_pairs_chain_impl(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
@@ -1081,7 +1196,8 @@ static int chain_unpack_count_impl(const uint64_t* d_recv, int32_t world, int32_
                                      void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
                                      int32_t* d_flag, const int64_t* d_x_off,
                                      const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
-                                     int64_t image_bound, uint64_t* d_out, void* stream) {
+                                     int64_t image_bound, uint64_t* d_out, void* stream,
+                                     void* d_work = nullptr) {
   TW_ARG_CHECK(world >= 1 && steps >= 0 && steps <= kChainMax && cap >= 1 && n_x >= 0 &&
                    n_z >= 0 && (half == 0 || half == 1) && (int64_t)world * steps < 65536 &&
                    x_shard >= 0 && z_shard >= 0 && n_shards >= 0 && n_shards < kEmMaxBig &&
@@ -1106,6 +1222,9 @@ static int chain_unpack_count_impl(const uint64_t* d_recv, int32_t world, int32_
                      cap, half ? 2 : 1, (int)half, n_x, n_z, x_shard, z_shard, (int)n_shards,
                      d_x_bag, (uint32_t*)d_z_bag, (unsigned*)d_cursors, d_flag);
   TW_LAUNCH_CHECK();
+  if (d_work != nullptr)  // (tw_chain_unpack_count_planes; its workspace checked there)
+    return count_chain_launch_work(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
+                                   max_nx, max_nz, half, image_bound, d_out, d_work, st);
   return count_chain_launch(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
                             max_nx, max_nz, half, image_bound, d_out, st);
 }
@@ -1197,7 +1316,133 @@ static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64
   TW_LAUNCH_CHECK();
   return TW_OK;
 }
+
+// The plane pre-pass and the count on its planes, back to back on st (out already zeroed)
+template <int NB>
+static void count_chain_launch_planes(const PlanesPlan& p, const float* xb,
+                                      const int64_t* d_x_off, int64_t x_stride, const float* zb,
+                                      const int64_t* d_z_off, int64_t z_stride, int n_shards,
+                                      int bags, uint32_t* work, unsigned long long* o,
+                                      hipStream_t st) {
+  const int64_t pre = ceil_div((int64_t)bags * (p.gx + p.gz), kBlock / kWave);
+  hipLaunchKernelGGL((k_chain_planes<NB>), dim3((unsigned)pre), dim3(kBlock), 0, st, xb, d_x_off,
+                     x_stride, zb, d_z_off, z_stride, n_shards, bags, p.gx, p.gz, p.swap,
+                     work);
+  const int64_t blocks = ceil_div((int64_t)bags * p.per_bag, kBlock / kWave);
+  hipLaunchKernelGGL((k_count_chain_planes<NB>), dim3((unsigned)blocks), dim3(kBlock), 0, st, xb,
+                     d_x_off, x_stride, zb, d_z_off, z_stride, n_shards, bags, p,
+                     (const uint32_t*)work, o);
+}
+
+// Bytes of plane workspace a bounded strict count of these bags may use (0: it runs packed)
+static int64_t chain_planes_work_bytes(int64_t bags, int64_t max_nx, int64_t max_nz,
+                                       int32_t half, int64_t image_bound) {
+  const int nb = half ? 0 : bits_pick_nb(image_bound);
+  if (nb == 0 || bags == 0 || max_nx == 0 || max_nz == 0) return 0;
+  return planes_work_words(max_nx, max_nz, bags, nb) * (int64_t)sizeof(uint32_t);
+}
+
+// The count launch of the _planes entries on an output already zeroed: where
+// count_chain_launch would run k_count_chain_bits, the pre-pass and k_count_chain_planes
+// (the same tuning hook: R = largest groups per item); everything else as count_chain_launch.
+static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
+                                   const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
+                                   int32_t n_shards, int32_t steps, int64_t max_nx,
+                                   int64_t max_nz, int32_t half, int64_t image_bound,
+                                   uint64_t* d_out, void* d_work, hipStream_t st) {
+  const int64_t bags = (int64_t)n_shards * steps;
+  if (max_nx == 0 || max_nz == 0) return TW_OK;
+  const int nb = plan_chain(max_nx, max_nz, bags, half != 0, bits_pick_nb(image_bound)).nb;
+  if (nb == 0)
+    return count_chain_launch(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride, n_shards,
+                              steps, max_nx, max_nz, half, -1, d_out, st);
+  const PlanesPlan p = planes_plan(max_nx, max_nz, bags,
+                                   g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0,
+                                   g_chain_zchunk, g_planes_swap);
+  TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
+                   bags * (int64_t)(p.gx + p.gz) < (1ll << 31),
+               "tw_count_pairs_chain_planes: grid too large");
+  auto* o = (unsigned long long*)d_out;
+  const float* xf = (const float*)d_x_bag;
+  const float* zf = (const float*)d_z_bag;
+  uint32_t* w = (uint32_t*)d_work;
+  if (nb == 16)
+    count_chain_launch_planes<16>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+                                  (int)bags, w, o, st);
+  else if (nb == 18)
+    count_chain_launch_planes<18>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+                                  (int)bags, w, o, st);
+  else if (nb == 20)
+    count_chain_launch_planes<20>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+                                  (int)bags, w, o, st);
+  else if (nb == 22)
+    count_chain_launch_planes<22>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+                                  (int)bags, w, o, st);
+  else
+    count_chain_launch_planes<24>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+                                  (int)bags, w, o, st);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
 }  // namespace tw
+
+extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
+                                              int64_t max_nz, int32_t half,
+                                              int64_t image_bound) {
+  if (n_shards < 0 || steps < 0 || max_nx < 0 || max_nz < 0) return 0;
+  return chain_planes_work_bytes((int64_t)n_shards * steps, max_nx, max_nz, half, image_bound);
+}
+
+// tw_count_pairs_chain_bound whose bit-sliced count reads planes built once per bag: the
+// pre-pass (k_chain_planes) and the count (k_count_chain_planes) back to back on the stream.
+// d_work: tw_chain_planes_work_bytes(...) bytes, written and read inside this call only.
+extern "C" int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off,
+                                           int64_t x_stride, const void* d_z_bag,
+                                           const int64_t* d_z_off, int64_t z_stride,
+                                           int32_t n_shards, int32_t steps, int64_t max_nx,
+                                           int64_t max_nz, int32_t half, int64_t image_bound,
+                                           uint64_t* d_out, void* stream, void* d_work,
+                                           int64_t work_bytes) {
+  TW_ARG_CHECK(image_bound >= 0, "tw_count_pairs_chain_planes: image_bound >= 0");
+  TW_ARG_CHECK(n_shards >= 0 && steps >= 0 && max_nx >= 0 && max_nz >= 0 && x_stride >= 0 &&
+                   z_stride >= 0 && (half == 0 || half == 1),
+               "tw_count_pairs_chain_planes: bad sizes");
+  TW_ARG_CHECK(max_nz < (1ll << 24), "tw_count_pairs_chain_planes: shards of < 2^24 z-images");
+  const int64_t bags = (int64_t)n_shards * steps;
+  if (bags == 0) return TW_OK;
+  const int64_t need = chain_planes_work_bytes(bags, max_nx, max_nz, half, image_bound);
+  TW_ARG_CHECK(work_bytes >= need && (need == 0 || d_work != nullptr),
+               "tw_count_pairs_chain_planes: work_bytes %lld < %lld (tw_chain_planes_work_bytes)",
+               (long long)work_bytes, (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  TW_HIP_CHECK(tw_zero_async(d_out, 0, sizeof(uint64_t) * (size_t)bags, st));
+  return count_chain_launch_work(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride,
+                                 n_shards, steps, max_nx, max_nz, half, image_bound, d_out,
+                                 d_work, st);
+}
+
+// tw_chain_unpack_count_bound with tw_count_pairs_chain_planes' count
+extern "C" int tw_chain_unpack_count_planes(const uint64_t* d_recv, int32_t world, int32_t steps,
+                                            int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
+                                            int64_t x_shard, int64_t z_shard, int32_t n_shards,
+                                            void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
+                                            int32_t* d_flag, const int64_t* d_x_off,
+                                            const int64_t* d_z_off, int64_t max_nx,
+                                            int64_t max_nz, int64_t image_bound, uint64_t* d_out,
+                                            void* stream, void* d_work, int64_t work_bytes) {
+  TW_ARG_CHECK(image_bound >= 0, "tw_chain_unpack_count_planes: image_bound >= 0");
+  TW_ARG_CHECK(n_shards >= 0 && steps >= 0 && max_nx >= 0 && max_nz >= 0 &&
+                   (half == 0 || half == 1),
+               "tw_chain_unpack_count_planes: bad sizes");
+  const int64_t need =
+      chain_planes_work_bytes((int64_t)n_shards * steps, max_nx, max_nz, half, image_bound);
+  TW_ARG_CHECK(work_bytes >= need && (need == 0 || d_work != nullptr),
+               "tw_chain_unpack_count_planes: work_bytes %lld < %lld "
+               "(tw_chain_planes_work_bytes)", (long long)work_bytes, (long long)need);
+  return chain_unpack_count_impl(d_recv, world, steps, cap, half, n_x, n_z, x_shard, z_shard,
+                                 n_shards, d_x_bag, d_z_bag, d_cursors, d_flag, d_x_off, d_z_off,
+                                 max_nx, max_nz, image_bound, d_out, stream, d_work);
+}
 
 // ----------------------------------------------------------------------------- exact count
 // The exact O(n + m) count of the bags (algo="sorted", row f4) on the rank images themselves:
@@ -1342,11 +1587,17 @@ extern "C" int tw_count_pairs_chain_bucket(const void* d_x_bag, const int64_t* d
 }
 
 extern "C" int tw_count_chain_set_plan(int32_t R, int64_t z_chunk) {
-  TW_ARG_CHECK(R == 0 || R == 8 || R == 16 || R == 2 || R == 4,
-               "tw_count_chain_set_plan: R in {0, 8, 16} (packed) or {2, 4} (bit-sliced)");
+  TW_ARG_CHECK(R == 0 || R == 8 || R == 16 || (R >= 2 && R <= 4),
+               "tw_count_chain_set_plan: R in {0, 8, 16} (packed) or {2, 3, 4} (bit-sliced)");
   TW_ARG_CHECK(z_chunk >= 0 && z_chunk <= (1ll << 24), "tw_count_chain_set_plan: bad z_chunk");
   g_chain_R = R;
   g_chain_zchunk = z_chunk;
+  return TW_OK;
+}
+
+extern "C" int tw_count_chain_set_swap(int32_t swap) {
+  TW_ARG_CHECK(swap >= 0 && swap <= 2, "tw_count_chain_set_swap: 0, 1 or 2");
+  g_planes_swap = swap;
   return TW_OK;
 }
 

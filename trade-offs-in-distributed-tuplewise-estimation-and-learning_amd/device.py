@@ -257,10 +257,13 @@ class HipOps:
         cur = self._unpack_cursors(int(steps) * 2 * (int(n_shards) + 1), x_bag.device)
         bound = self.image_bound
         if bound is not None and not half:
-            L.call("tw_chain_unpack_count_bound", L.ptr(recv), int(world), int(steps), int(cap),
-                   0, int(n), int(m), int(kx), int(kz), int(n_shards), L.ptr(x_bag),
+            st = L.stream_handle()
+            work, wb = self._planes_work(n_shards, steps, max_nx, max_nz, bound, st,
+                                         x_bag.device)
+            L.call("tw_chain_unpack_count_planes", L.ptr(recv), int(world), int(steps),
+                   int(cap), 0, int(n), int(m), int(kx), int(kz), int(n_shards), L.ptr(x_bag),
                    L.ptr(z_bag), L.ptr(cur), L.ptr(flag), L.ptr(x_off_dev), L.ptr(z_off_dev),
-                   int(max_nx), int(max_nz), int(bound), L.ptr(out), L.stream_handle())
+                   int(max_nx), int(max_nz), int(bound), L.ptr(out), st, L.ptr(work), wb)
             return out
         L.call("tw_chain_unpack_count", L.ptr(recv), int(world), int(steps), int(cap),
                int(bool(half)), int(n), int(m), int(kx), int(kz), int(n_shards), L.ptr(x_bag),
@@ -299,7 +302,8 @@ class HipOps:
     # The caller's promise for the next count_chain / chain_unpack_count: every rank image of
     # the bags is an integer in [0, image_bound] (x: or the "never" image).  Set around a call
     # by bounded_images(); None: no promise, the packed kernel.  With a bound and the strict
-    # predicate the counts run bit-sliced (tw_count_pairs_chain_bound).
+    # predicate the counts run bit-sliced on planes built once per bag
+    # (tw_count_pairs_chain_planes / tw_chain_unpack_count_planes).
     image_bound = None
 
     @contextlib.contextmanager
@@ -317,14 +321,40 @@ class HipOps:
             self._cursors = c = self.t.empty((max(words, 1024),), dtype=self.t.int32, device=dev)
         return c
 
+    def _planes_work(self, n_shards, steps, max_nx, max_nz, bound, st, dev):
+        """The plane workspace of a bounded strict count issued on stream `st` (a raw handle)
+        and its size in bytes.  The contract: the workspace is written (the
+        pre-pass) and read (the count) inside ONE native call on ONE stream, so calls on one
+        stream reuse it in stream order; counts issued from different streams may overlap on
+        the device and must not share it, hence one buffer per (device, stream handle), grown
+        as needed.  It is never allocated inside a graph capture: a capture that needs a
+        larger one than an eager call has left raises (run the call once eagerly first).
+        Every caller in this module — local_counts and _unn_many_chain's count / unpack +
+        count — issues the op on the current stream and passes that same handle here."""
+        wb = int(L.lib().tw_chain_planes_work_bytes(int(n_shards), int(steps), int(max_nx),
+                                                    int(max_nz), 0, int(bound)))
+        pool = self.__dict__.setdefault("_planes_pool", {})
+        key = (dev.index, st.value)
+        w = pool.get(key)
+        if w is None or w.numel() < wb:
+            if self.t.cuda.is_current_stream_capturing():
+                raise RuntimeError("tuplewise: the plane workspace must exist before a graph "
+                                   "capture (run the count once eagerly first)")
+            pool[key] = None  # release the smaller one first
+            pool[key] = w = self.t.empty((max(wb, 256),), dtype=self.t.uint8, device=dev)
+        return w, wb
+
     def count_chain(self, x_bag, x_off_dev, z_bag, z_off_dev, n_shards, steps, x_stride,
                     z_stride, max_nx, max_nz, half, out):
         """Counts of steps x n_shards bags in one launch into out (steps, n_shards)."""
         bound = self.image_bound
         if bound is not None and not half:
-            L.call("tw_count_pairs_chain_bound", L.ptr(x_bag), L.ptr(x_off_dev), int(x_stride),
+            st = L.stream_handle()
+            work, wb = self._planes_work(n_shards, steps, max_nx, max_nz, bound, st,
+                                         x_bag.device)
+            L.call("tw_count_pairs_chain_planes", L.ptr(x_bag), L.ptr(x_off_dev), int(x_stride),
                    L.ptr(z_bag), L.ptr(z_off_dev), int(z_stride), int(n_shards), int(steps),
-                   int(max_nx), int(max_nz), 0, int(bound), L.ptr(out), L.stream_handle())
+                   int(max_nx), int(max_nz), 0, int(bound), L.ptr(out), st, L.ptr(work), wb)
             return out
         L.call("tw_count_pairs_chain", L.ptr(x_bag), L.ptr(x_off_dev), int(x_stride),
                L.ptr(z_bag), L.ptr(z_off_dev), int(z_stride), int(n_shards), int(steps),
