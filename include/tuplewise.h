@@ -222,7 +222,9 @@ int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off, int
                                 int32_t half, int64_t image_bound, uint64_t* d_out,
                                 void* stream, void* d_work, int64_t work_bytes);
 /* Bytes of d_work for tw_count_pairs_chain_planes / tw_chain_unpack_count_planes on steps x
- * n_shards bags of at most max_nx x max_nz images (0 where the count runs packed). */
+ * n_shards bags of at most max_nx x max_nz images (0 where the count runs packed): the planes
+ * and the class-run form's regions (the class-ordered z images and the run
+ * tables), sized for any plan and any class bits, so the tuning hooks do not change it. */
 int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
                                    int64_t max_nz, int32_t half, int64_t image_bound);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
@@ -249,6 +251,13 @@ int tw_count_chain_set_plan(int32_t R, int64_t z_chunk);
  * (no swapped items), 2 swaps wherever chainplan.h's per-bag rule allows, 1 (default) does so
  * in launches large enough to gain from it.  Process-global; same counts. */
 int tw_count_chain_set_swap(int32_t swap);
+/* A/B hook for tw_count_pairs_chain_planes' class-run form: the z images of a
+ * bag grouped by their top k bits once per launch (k_chain_zclasses) and counted run by run of
+ * one class (k_count_chain_classes), the class's top-field compare hoisted out of the per-z
+ * loop.  k = -1 (default) chooses by chainclass.h's rule, 0 turns classes off
+ * (k_count_chain_planes), 1 <= k <= 8 forces k class bits; anything else is TW_ERR_ARG.
+ * Process-global; same counts. */
+int tw_count_chain_set_class_bits(int32_t k);
 /* The scores in their final order after the chains (one process): d_x_out[d_x_pos[e]] =
  * d_x[e] (8-B values), likewise for Z. */
 int tw_chain_scatter(const void* d_x, const uint32_t* d_x_pos, int64_t n_x, const void* d_z,

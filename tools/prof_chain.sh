@@ -16,4 +16,7 @@ timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INST
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU --output-format csv -d $O/p4 -o run -- $B > $O.p4.log 2>&1
 python3 tools/pmc_summary.py $O/chain_count_pmc.json k_count_chain $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null
 python3 tools/pmc_summary.py $O/chain_emit_pmc.json k_chain_emit $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null
+# the count's pre-passes (the planes; with class bits the class-ordered z and the run tables)
+python3 tools/pmc_summary.py $O/chain_planes_pmc.json k_chain_planes $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null
+python3 tools/pmc_summary.py $O/chain_zclasses_pmc.json k_chain_zclasses $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null 2>&1 || true  # (none without class bits)
 echo done

@@ -17,27 +17,38 @@ PAIRS_PER_STEP = 64 * 15625 * 15625  # n = 1e6/class, N = 64 shards
 PEAK = 256 * 64 * 2.4e9  # lane-op/s
 
 path, K, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
-# (the strict count: the packed k_count_chain<R, false>, the bit-sliced k_count_chain_bits<NB, R>
-# or the plane-reading k_count_chain_planes<NB>, whose launch's time includes its pre-pass
-# k_chain_planes<NB>, the launch just before it on the stream)
+# (the strict count: the packed k_count_chain<R, false>, the bit-sliced k_count_chain_bits<NB, R>,
+# the plane-reading k_count_chain_planes<NB>, whose launch's time includes its pre-pass
+# k_chain_planes<NB>, the launch just before it on the stream, or its class-run form
+# k_count_chain_classes<NB, K>, whose time includes both pre-passes: k_chain_planes<NB> and
+# k_chain_zclasses)
 every = list(csv.DictReader(open(path)))
 rows = [r for r in every
         if ("k_count_chain<" in r["Kernel_Name"] and ", false>" in r["Kernel_Name"])
         or "k_count_chain_bits<" in r["Kernel_Name"]
-        or "k_count_chain_planes<" in r["Kernel_Name"]]
+        or "k_count_chain_planes<" in r["Kernel_Name"]
+        or "k_count_chain_classes<" in r["Kernel_Name"]]
 pre = sorted((r for r in every if "k_chain_planes<" in r["Kernel_Name"]),
              key=lambda r: int(r["Start_Timestamp"]))
+pre2 = sorted((r for r in every if "k_chain_zclasses" in r["Kernel_Name"]),
+              key=lambda r: int(r["Start_Timestamp"]))
 grid = lambda r: int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)
 dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
 g = max(grid(r) for r in rows)
 big = sorted((r for r in rows if grid(r) == g), key=lambda r: int(r["Start_Timestamp"]))
 
 
+def last_before(qs, r):
+    before = [q for q in qs if int(q["Start_Timestamp"]) < int(r["Start_Timestamp"])]
+    return dur(before[-1]) if before else 0.0
+
+
 def prepass_ms(r):
+    if "k_count_chain_classes<" in r["Kernel_Name"]:
+        return last_before(pre, r) + last_before(pre2, r)
     if "k_count_chain_planes<" not in r["Kernel_Name"]:
         return 0.0
-    before = [q for q in pre if int(q["Start_Timestamp"]) < int(r["Start_Timestamp"])]
-    return dur(before[-1]) if before else 0.0
+    return last_before(pre, r)
 
 
 pre_ds = [prepass_ms(r) for r in big]

@@ -65,6 +65,7 @@ _SIGNATURES = {
                                     _i32, _vp, _vp],
     "tw_count_chain_set_plan": [_i32, _i64],
     "tw_count_chain_set_swap": [_i32],
+    "tw_count_chain_set_class_bits": [_i32],
     "tw_chain_set_emit": [_i32, _i32],
     "tw_chain_scatter": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp],
     "tw_count_pairs_sorted_work_bytes": [_i32, _i64],

@@ -32,6 +32,7 @@
 // (tw_rank_images_query with half = 1), and ONE clamped packed add gives [x > z] and [x >= z]
 // for a z: clamp(h(x) - g(z)) == 1 <=> x >= z.  Half units = the sum of both lanes.
 #include "bitcount.h"
+#include "chainclass.h"
 #include "chainplan.h"
 #include "feistel.h"
 #include "pkcount.h"
@@ -647,6 +648,151 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_planes(
   count_chain_epilogue(tot, active, v, wid, lane, out);
 }
 
+// The class-run form of that count (chainclass.h).  Pre-pass 2, one block per
+// bag: the bag's z images, complemented (bits_z_image), are counting-sorted by class — the top
+// cp.k of their low nb bits — into the class-ordered region of the workspace, and the bag's run
+// table is written: per non-empty class ceil(n_c / cp.chunk) runs of near-equal length.  Two
+// passes over the images in global memory (histogram; scatter through LDS cursors), so a bag
+// of any size goes through; the order inside a class is that of the cursors' atomics, which
+// the counts — integer sums — do not see.
+__device__ __forceinline__ uint32_t class_block_scan(uint32_t v, uint32_t* wsum, int lane,
+                                                     int wid) {
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const uint32_t t = __shfl_up(v, o, kWave);
+    if (lane >= o) v += t;
+  }
+  if (lane == kWave - 1) wsum[wid] = v;
+  __syncthreads();
+  uint32_t add = 0;
+  for (int w = 0; w < wid; ++w) add += wsum[w];
+  __syncthreads();
+  return v + add;  // inclusive
+}
+
+__global__ __launch_bounds__(kBlock) void k_chain_zclasses(
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int nb, ClassPlan cp, uint32_t* __restrict__ work) {
+  static_assert(kBlock == 1 << kClassMaxBits, "one thread per class");
+  __shared__ uint32_t hist[kBlock], wsum[kBlock / kWave];
+  const int t = threadIdx.x, lane = t & (kWave - 1), wid = t / kWave;
+  const int v = blockIdx.x;  // < n_bags
+  const int c = v / n_shards, s = v - c * n_shards;
+  const int64_t nz = z_off[s + 1] - z_off[s];
+  const float* __restrict__ src = zb + ((int64_t)c * z_stride + z_off[s]);
+  hist[t] = 0;
+  __syncthreads();
+  constexpr int U = 8;  // loads in flight per thread: a block walks its whole bag
+  for (int64_t i0 = t; i0 < nz; i0 += kBlock * U) {
+    float f[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f[u] = src[min(i0 + u * kBlock, nz - 1)];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (i0 + u * kBlock < nz) atomicAdd(&hist[class_of(bits_z_image(f[u]), nb, cp.k)], 1u);
+  }
+  __syncthreads();
+  const uint32_t n = hist[t];  // (classes >= 2^k: 0)
+  const uint32_t nr = (uint32_t)class_runs(n, cp.chunk);
+  const uint32_t c0 = class_block_scan(n, wsum, lane, wid) - n;
+  const uint32_t e1 = class_block_scan(nr, wsum, lane, wid), e0 = e1 - nr;
+  hist[t] = c0;  // now the class's cursor (every thread read its own count above)
+  if (t == kBlock - 1) work[cp.off_cnt + v] = e1;  // <= cp.cap (class_capacity)
+  uint32_t* __restrict__ tab = work + (cp.off_tab + (int64_t)v * 2 * cp.cap);
+  for (uint32_t j = 0; j < nr; ++j) {
+    const ClassRun r = class_run(c0, n, nr, j, (uint32_t)t);
+    tab[2 * (e0 + j)] = class_entry_lo(r);
+    tab[2 * (e0 + j) + 1] = class_entry_hi(r);
+  }
+  __syncthreads();
+  uint32_t* __restrict__ zs = work + (cp.off_zs + (int64_t)v * cp.zs_stride);
+  for (int64_t i0 = t; i0 < nz; i0 += kBlock * U) {
+    float f[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f[u] = src[min(i0 + u * kBlock, nz - 1)];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t zc = bits_z_image(f[u]);
+      if (i0 + u * kBlock < nz)
+        zs[atomicAdd(&hist[class_of(zc, nb, cp.k)], 1u)] = zc;  // < c0 + n <= nz
+    }
+  }
+}
+
+// The count: per bag p.tiles_x x cp.cap class items (tile-major: a block's waves read the same
+// planes), then the swapped items of the plan unchanged (full-NB loop on the z planes).  A
+// class item whose entry is past the bag's count exits at once; an active one reads its run
+// {z0, len, class} and counts its up to p.R x groups against exactly those len images.
+template <int NB, int K>
+__global__ __launch_bounds__(kBlock) void k_count_chain_classes(
+    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const int64_t* __restrict__ z_off, int n_shards, int n_bags, PlanesPlan p, ClassPlan cp,
+    const uint32_t* __restrict__ work, unsigned long long* __restrict__ out) {
+  const int lb = xcd_block(blockIdx.x, gridDim.x);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int item = lb * (kBlock / kWave) + wid;
+  const int v = item / cp.per_bag;
+  bool active = v < n_bags;
+  unsigned long long tot = 0;
+  if (active) {
+    const int c = v / n_shards, s = v - c * n_shards;
+    const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
+    const int rem = item - v * cp.per_bag;
+    const int n_class = p.tiles_x * cp.cap;
+    if (rem < n_class) {
+      const int tx = rem / cp.cap, e = rem - tx * cp.cap;
+      const PlanesBag bag = planes_bag(nx, nz, p.swap != 0);
+      const int lim = bag.xgroups < p.gx ? bag.xgroups : p.gx;
+      const int g0 = tx * p.R;
+      const int ng = __builtin_amdgcn_readfirstlane(lim - g0 < p.R ? lim - g0 : p.R);
+      active = ng > 0 && e < (int)work[cp.off_cnt + v];
+      if (active) {
+        const uint32_t* __restrict__ tab = work + (cp.off_tab + ((int64_t)v * cp.cap + e) * 2);
+        const ClassRun r = class_entry((uint32_t)__builtin_amdgcn_readfirstlane((int)tab[0]),
+                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[1]));
+        const uint32_t* __restrict__ pw =
+            work + bits_uniform(planes_word(NB, (int64_t)v * p.gx + g0, 0, 0));
+        const uint32_t* __restrict__ zs =
+            work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride + r.z0);
+        const int len = (int)r.len;  // >= 1: only non-empty classes have runs
+        unsigned long long t;
+        if (ng == 4)
+          t = bits_count_class<NB, K, 4>(pw, zs, len, r.cls, lane);
+        else if (ng == 3)
+          t = bits_count_class<NB, K, 3>(pw, zs, len, r.cls, lane);
+        else if (ng == 2)
+          t = bits_count_class<NB, K, 2>(pw, zs, len, r.cls, lane);
+        else
+          t = bits_count_class<NB, K, 1>(pw, zs, len, r.cls, lane);
+        tot = wave_sum_u64(t);
+      }
+    } else {
+      const PlanesItem it = planes_item(p, nx, nz, p.tiles_x * p.zchunks + (rem - n_class));
+      active = it.active;  // (swapped: rem past the plan's plane items)
+      if (active) {
+        const int64_t group = (int64_t)n_bags * p.gx + (int64_t)v * p.gz + it.g0;
+        const uint32_t* __restrict__ pw = work + bits_uniform(planes_word(NB, group, 0, 0));
+        const float* __restrict__ sf =
+            xb + bits_uniform((int64_t)c * x_stride + x_off[s] + it.s0);
+        const int ns = __builtin_amdgcn_readfirstlane((int)(it.s1 - it.s0));
+        const int ng = __builtin_amdgcn_readfirstlane(it.ng);
+        unsigned long long t;
+        if (ng == 4)
+          t = bits_count_planes<NB, 4>(pw, sf, ns, true, lane);
+        else if (ng == 3)
+          t = bits_count_planes<NB, 3>(pw, sf, ns, true, lane);
+        else if (ng == 2)
+          t = bits_count_planes<NB, 2>(pw, sf, ns, true, lane);
+        else
+          t = bits_count_planes<NB, 1>(pw, sf, ns, true, lane);
+        tot = wave_sum_u64(t);
+      }
+    }
+  }
+  count_chain_epilogue(tot, active, v, wid, lane, out);
+}
+
 // ------------------------------------------- the call's final arrays over ranks: one exchange
 // (round 6) Every rank walked its own elements to their final global positions (the chains'
 // state after the call's last emission); each element's score and rank-image record travel
@@ -788,6 +934,7 @@ struct ChainPlan {
 static int g_chain_R = 0;  // tuning hooks (tw_count_chain_set_plan); 0 = automatic
 static int64_t g_chain_zchunk = 0;
 static int g_planes_swap = 1;  // (tw_count_chain_set_swap: 0 never, 1 automatic, 2 always)
+static int g_class_bits = -1;  // (tw_count_chain_set_class_bits: -1 automatic, 0 off, 1..8)
 
 // strict: R in {16, 8} x-images per lane, least padded slots (ties to 16); half: R = 8 {g, h}
 // pairs (the same 8 packed registers per lane).  z chunks: as many as give ~150 work items per
@@ -1317,9 +1464,10 @@ static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64
   return TW_OK;
 }
 
-// The plane pre-pass and the count on its planes, back to back on st (out already zeroed)
+// The plane pre-pass and the count on its planes, back to back on st (out already zeroed);
+// with class bits (cp.k > 0) pre-pass 2 between them and the count on class runs
 template <int NB>
-static void count_chain_launch_planes(const PlanesPlan& p, const float* xb,
+static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, const float* xb,
                                       const int64_t* d_x_off, int64_t x_stride, const float* zb,
                                       const int64_t* d_z_off, int64_t z_stride, int n_shards,
                                       int bags, uint32_t* work, unsigned long long* o,
@@ -1328,6 +1476,22 @@ static void count_chain_launch_planes(const PlanesPlan& p, const float* xb,
   hipLaunchKernelGGL((k_chain_planes<NB>), dim3((unsigned)pre), dim3(kBlock), 0, st, xb, d_x_off,
                      x_stride, zb, d_z_off, z_stride, n_shards, bags, p.gx, p.gz, p.swap,
                      work);
+  if (cp.k > 0) {  // the class-run form: pre-pass 2, then the count on class runs
+    hipLaunchKernelGGL(k_chain_zclasses, dim3((unsigned)bags), dim3(kBlock), 0, st, zb, d_z_off,
+                       z_stride, n_shards, bags, NB, cp, work);
+    const dim3 g((unsigned)ceil_div((int64_t)bags * cp.per_bag, kBlock / kWave)), b(kBlock);
+#define TW_CLASS_CASE(K)                                                                       \
+  case K:                                                                                      \
+    hipLaunchKernelGGL((k_count_chain_classes<NB, K>), g, b, 0, st, xb, d_x_off, x_stride,     \
+                       d_z_off, n_shards, bags, p, cp, (const uint32_t*)work, o);              \
+    break;
+    switch (cp.k) {
+      TW_CLASS_CASE(1) TW_CLASS_CASE(2) TW_CLASS_CASE(3) TW_CLASS_CASE(4)
+      TW_CLASS_CASE(5) TW_CLASS_CASE(6) TW_CLASS_CASE(7) TW_CLASS_CASE(8)
+    }
+#undef TW_CLASS_CASE
+    return;
+  }
   const int64_t blocks = ceil_div((int64_t)bags * p.per_bag, kBlock / kWave);
   hipLaunchKernelGGL((k_count_chain_planes<NB>), dim3((unsigned)blocks), dim3(kBlock), 0, st, xb,
                      d_x_off, x_stride, zb, d_z_off, z_stride, n_shards, bags, p,
@@ -1339,12 +1503,15 @@ static int64_t chain_planes_work_bytes(int64_t bags, int64_t max_nx, int64_t max
                                        int32_t half, int64_t image_bound) {
   const int nb = half ? 0 : bits_pick_nb(image_bound);
   if (nb == 0 || bags == 0 || max_nx == 0 || max_nz == 0) return 0;
-  return planes_work_words(max_nx, max_nz, bags, nb) * (int64_t)sizeof(uint32_t);
+  // (the class regions sized for any class bits and plan: chainclass.h's class_work_words)
+  return (planes_work_words(max_nx, max_nz, bags, nb) + class_work_words(max_nz, bags)) *
+         (int64_t)sizeof(uint32_t);
 }
 
 // The count launch of the _planes entries on an output already zeroed: where
 // count_chain_launch would run k_count_chain_bits, the pre-pass and k_count_chain_planes
-// (the same tuning hook: R = largest groups per item); everything else as count_chain_launch.
+// (the same tuning hook: R = largest groups per item) or, with class bits, its class-run form
+// (chainclass.h); everything else as count_chain_launch.
 static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                                    const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                                    int32_t n_shards, int32_t steps, int64_t max_nx,
@@ -1359,27 +1526,32 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   const PlanesPlan p = planes_plan(max_nx, max_nz, bags,
                                    g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0,
                                    g_chain_zchunk, g_planes_swap);
+  // class bits: forced (clamped to this launch's planes), or chainclass.h's automatic rule
+  const int k = g_class_bits < 0 ? class_bits_auto(max_nz, bags, nb)
+                                 : std::min(g_class_bits, std::min(kClassMaxBits, nb - 8));
+  const ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k);
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
-                   bags * (int64_t)(p.gx + p.gz) < (1ll << 31),
+                   bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&
+                   bags * (int64_t)cp.per_bag < (1ll << 31),
                "tw_count_pairs_chain_planes: grid too large");
   auto* o = (unsigned long long*)d_out;
   const float* xf = (const float*)d_x_bag;
   const float* zf = (const float*)d_z_bag;
   uint32_t* w = (uint32_t*)d_work;
   if (nb == 16)
-    count_chain_launch_planes<16>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<16>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else if (nb == 18)
-    count_chain_launch_planes<18>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<18>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else if (nb == 20)
-    count_chain_launch_planes<20>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<20>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else if (nb == 22)
-    count_chain_launch_planes<22>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<22>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else
-    count_chain_launch_planes<24>(p, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<24>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   TW_LAUNCH_CHECK();
   return TW_OK;
@@ -1598,6 +1770,13 @@ extern "C" int tw_count_chain_set_plan(int32_t R, int64_t z_chunk) {
 extern "C" int tw_count_chain_set_swap(int32_t swap) {
   TW_ARG_CHECK(swap >= 0 && swap <= 2, "tw_count_chain_set_swap: 0, 1 or 2");
   g_planes_swap = swap;
+  return TW_OK;
+}
+
+extern "C" int tw_count_chain_set_class_bits(int32_t k) {
+  TW_ARG_CHECK(k >= -1 && k <= kClassMaxBits,
+               "tw_count_chain_set_class_bits: -1 (automatic), 0 (off) or 1 .. 8");
+  g_class_bits = k;
   return TW_OK;
 }
 
