@@ -350,9 +350,11 @@ int tw_count_pairs_idx(const void* d_x, const void* d_z, const int64_t* d_ix,
  * d_work == NULL this call runs tw_count_pairs_idx. */
 /* Tuning hook of tw_count_pairs_idx_ws: blocks of 1024 threads per shard (0 = the plan's). */
 int tw_count_idx_set_parts(int32_t parts);
-/* Tuning hook of the int32-index ranked count: 0 = four 16-B loads of each index stream in
- * flight per thread (default), 1 = the same as nontemporal loads, 2/3 = eight loads (plain /
- * nontemporal), 4/5 = two loads.  Process-global; results do not depend on it. */
+/* Tuning hook of the int32-index ranked count (16-B aligned index streams): 0 = two 16-B loads of
+ * each index stream per thread and batch, pipelined: the next batch is issued before the
+ * previous one is compared (default), 1 = the same as nontemporal loads, 2/3 = four loads in one
+ * buffer, not pipelined (plain / nontemporal), 4/5 = four loads, pipelined (plain /
+ * nontemporal).  Process-global; results do not depend on it. */
 int tw_count_idx_set_variant(int32_t v);
 int tw_count_pairs_idx_ws(const void* d_x, const int64_t* d_x_off, const void* d_z,
                           const int64_t* d_z_off, int32_t n_shards, int64_t max_nx,

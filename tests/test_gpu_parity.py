@@ -383,10 +383,16 @@ def test_exchange_kernels_simulated_ranks(gpu):
     is a host-side regrouping): send counts, receive counts from the inverse permutation,
     block-reserved bucket scatter with a position base, scatter into place == the global
     permutation of the oracle."""
+    exchange_kernels_body(5, 30_011)
+
+
+def exchange_kernels_body(G, n_loc):
+    """The body of test_exchange_kernels_simulated_ranks for G ranks of n_loc elements (shared
+    with the launch-plan sweep, tests/test_gpu_plan_sweep.py)."""
     import torch
     from tuplewise.device import HipOps
     ops = HipOps()
-    G, n_loc, key = 5, 30_011, 0xDEADBEEF
+    key = 0xDEADBEEF
     n_tot = G * n_loc
     rng = np.random.RandomState(1)
     vals = rng.normal(size=n_tot)
@@ -699,10 +705,16 @@ def test_fused_exchange_kernels_simulated_ranks(gpu):
     the oracle's forward/inverse permutation histograms, every bucket [X records | Z records],
     and after the (host-side) all-to-all and the scatter both samples equal the oracle's
     global permutations."""
+    fused_exchange_kernels_body(3, 20_011, 7_003)
+
+
+def fused_exchange_kernels_body(G, n_loc, m_loc):
+    """The body of test_fused_exchange_kernels_simulated_ranks (shared with the launch-plan
+    sweep, tests/test_gpu_plan_sweep.py)."""
     import torch
     from tuplewise.device import HipOps
     ops = HipOps()
-    G, n_loc, m_loc, kx, kz = 3, 20_011, 7_003, 101, 202
+    kx, kz = 101, 202
     rng = np.random.RandomState(4)
     X, Z = rng.normal(size=G * n_loc), rng.normal(size=G * m_loc)
     want_x, want_z = O.permute_scatter(X, kx), O.permute_scatter(Z, kz)
@@ -740,6 +752,12 @@ def test_fixed_exchange_kernels_simulated_ranks(gpu, G, n_loc, m_loc):
     histograms, the equal-split all-to-all is done on the host, and after the scatter both
     samples equal the oracle's global permutations; a capacity below a bucket's size raises
     the flag on both sides (never a silent drop)."""
+    fixed_exchange_kernels_body(G, n_loc, m_loc)
+
+
+def fixed_exchange_kernels_body(G, n_loc, m_loc):
+    """The body of test_fixed_exchange_kernels_simulated_ranks (shared with the launch-plan
+    sweep, tests/test_gpu_plan_sweep.py)."""
     import torch
     from tuplewise.device import HipOps
     ops = HipOps()
