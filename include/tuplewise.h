@@ -249,7 +249,9 @@ int tw_chain_set_emit(int32_t epr, int32_t steps_per_round);
 int tw_count_chain_set_plan(int32_t R, int64_t z_chunk);
 /* A/B hook for tw_count_pairs_chain_planes: 0 counts every x remainder as a padded plane group
  * (no swapped items), 2 swaps wherever chainplan.h's per-bag rule allows, 1 (default) does so
- * in launches large enough to gain from it.  Process-global; same counts. */
+ * in launches large enough to gain from it and, under class runs, only where the swapped
+ * remainder also costs fewer instructions than a padded group (chainclass.h class_swap_mode,
+ * DESIGN §4.1h).  Process-global; same counts. */
 int tw_count_chain_set_swap(int32_t swap);
 /* A/B hook for tw_count_pairs_chain_planes' class-run form: the z images of a
  * bag grouped by their top k bits once per launch (k_chain_zclasses) and counted run by run of

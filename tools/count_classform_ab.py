@@ -1,0 +1,122 @@
+"""A/B of the class loop's build-time forms (csrc/chainclass.h TW_CLASS_FORM / TW_CLASS_BATCH,
+DESIGN §4.1h) on tools/count_classes_ab.py's shapes.  One fresh child process per variant
+library (`make -C <pkg>/csrc ab-classform` -> tools/variants/libtuplewise_classform*.so, chosen
+with TW_LIB_PATH; "product" is the library as built), the children alternated over REPS passes.
+Inside each child, tw_count_pairs_chain_planes with classes off (tw_count_chain_set_class_bits
+0: k_count_chain_planes, which no form touches — the in-process yardstick), under the automatic
+rule, and under automatic class bits with the x remainder never swapped
+(tw_count_chain_set_swap 0) and swapped wherever chainplan.h's per-bag rule allows (2),
+interleaved over 7 rounds; per setting the median, min and max ms of the whole native call
+(both pre-passes + count) and the ratio of medians to k = 0 of the same process.  Counts must
+agree exactly.
+Run on the GPU box:  python tools/count_classform_ab.py [out.json [variant ...]]
+(variants by file suffix, e.g. classform1 classform2b16; default: every library present)"""
+import json
+import os
+import pathlib
+import subprocess
+import sys
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+VARIANTS = ROOT / "tools" / "variants"
+ROUNDS, REPS = 7, 2
+SETTINGS = [("k=0", 0, 1), ("automatic", -1, 1), ("automatic, swap 0", -1, 0),
+            ("automatic, swap 2", -1, 2)]
+# (name, G, K): G ranks share the strong problem; G = 0: C2; G = -1: 64 bags per step of
+# 7 * 2048 + 100 x images, a remainder small enough that class_swap_mode keeps it swapped
+SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1, 4),
+          ("G=2 K=20", 2, 20), ("G=4 K=4", 4, 4), ("G=4 K=20", 4, 20), ("G=8 K=4", 8, 4),
+          ("G=8 K=20", 8, 20), ("C2", 0, 1), ("remainder 100 K=20", -1, 20)]
+
+
+def child():
+    sys.path.insert(0, str(ROOT))
+    import numpy as np
+    import torch
+
+    import tuplewise  # noqa: F401
+    from tuplewise import _lib as L
+    from tuplewise.device import prop_swor_layout
+
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    report = []
+    for name, G, K in SHAPES:
+        if G == 0:  # C2: one bag of 1e5 x 1e5
+            nl, Nl, bound = 100_000, 1, 100_000
+        elif G < 0:
+            nl, Nl, bound = 64 * (7 * 2048 + 100), 64, 1_000_000
+        else:  # a rank's share of the strong problem: images are ranks against all 1e6 Z
+            nl, Nl, bound = 1_000_000 // G, 64 // G, 1_000_000
+        x_off, z_off, _ = prop_swor_layout(nl, nl, Nl)
+        xo, zo = torch.from_numpy(x_off).cuda(), torch.from_numpy(z_off).cuda()
+        k, kz = int(np.diff(x_off).max()), int(np.diff(z_off).max())
+        xb = torch.randint(0, bound + 1, (K, nl), device="cuda", generator=gen).float()
+        zb = -torch.randint(0, bound + 1, (K, nl), device="cuda", generator=gen).float()
+        out = torch.empty((K, Nl), dtype=torch.int64, device="cuda")
+        wb = int(L.lib().tw_chain_planes_work_bytes(Nl, K, k, kz, 0, bound))
+        work = torch.empty(max(wb, 256), dtype=torch.uint8, device="cuda")
+        ts = {s[0]: [] for s in SETTINGS}
+        ref = None
+
+        def call():
+            L.call("tw_count_pairs_chain_planes", xb, xo, nl, zb, zo, nl, Nl, K, k, kz, 0, bound,
+                   out, L.stream_handle(), work, wb)
+        try:
+            for _ in range(ROUNDS):
+                for sname, bits, swap in SETTINGS:
+                    L.call("tw_count_chain_set_class_bits", bits)
+                    L.call("tw_count_chain_set_swap", swap)
+                    e0 = torch.cuda.Event(enable_timing=True)
+                    e1 = torch.cuda.Event(enable_timing=True)
+                    call()  # warm
+                    e0.record()
+                    call()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if ref is None:
+                        ref = out.clone()
+                    assert torch.equal(out, ref), (name, sname)
+                    ts[sname].append(e0.elapsed_time(e1))
+        finally:
+            L.call("tw_count_chain_set_class_bits", -1)
+            L.call("tw_count_chain_set_swap", 1)
+        ms = {s: {"median": float(np.median(t)), "min": float(min(t)), "max": float(max(t))}
+              for s, t in ts.items()}
+        report.append({"shape": name, "bags": K * Nl, "nx": k, "nz": kz, "ms": ms,
+                       "ratio to k=0": {s: ms[s]["median"] / ms["k=0"]["median"] for s in ms}})
+    print(json.dumps(report))
+
+
+def main():
+    out = sys.argv[1] if len(sys.argv) > 1 else None
+    libs = {"product": None}
+    for p in sorted(VARIANTS.glob("libtuplewise_classform*.so")):
+        libs[p.stem.replace("libtuplewise_", "")] = p
+    if len(sys.argv) > 2:
+        libs = {k: v for k, v in libs.items() if k in sys.argv[2:]}
+    passes = {k: [] for k in libs}
+    for rep in range(REPS):
+        for k, lib in libs.items():
+            env = dict(os.environ)
+            env.pop("TW_LIB_PATH", None)
+            if lib is not None:
+                env["TW_LIB_PATH"] = str(lib)
+            r = subprocess.run([sys.executable, __file__, "--child"], env=env,
+                               capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                print(k, "failed:", r.stderr[-1500:], flush=True)
+                sys.exit(1)
+            rows = json.loads(r.stdout.strip().splitlines()[-1])
+            passes[k].append(rows)
+            print(f"pass {rep} {k}: " + "  ".join(
+                f"{row['shape']} " + "/".join(f"{row['ratio to k=0'][s[0]]:.4f}"
+                                              for s in SETTINGS[1:]) for row in rows), flush=True)
+            if out:
+                pathlib.Path(out).write_text(json.dumps(
+                    {"what": "ratio of medians to k = 0 inside each child (automatic / swap 0 / "
+                             "swap 2 printed); one child per library and pass",
+                     "passes": passes}, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    child() if sys.argv[1:2] == ["--child"] else main()

@@ -719,75 +719,98 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
   }
 }
 
-// The count: per bag p.tiles_x x cp.cap class items (tile-major: a block's waves read the same
-// planes), then the swapped items of the plan unchanged (full-NB loop on the z planes).  A
-// class item whose entry is past the bag's count exits at once; an active one reads its run
-// {z0, len, class} and counts its up to p.R x groups against exactly those len images.
+// The count on class runs: per bag p.tiles_x x cp.cap class items (tile-major: a block's waves
+// read the same planes).  An item whose entry is past the bag's count exits at once; an active
+// one reads its run {z0, len, class} and counts its up to p.R x groups against exactly those
+// len images.  The plan's swapped items run in a launch of their own (k_count_chain_swapped):
+// their full-NB loop holds R * NB planes per lane, and without it this kernel allocates 89
+// VGPRs at NB = 20, k = 8 (at most 94 at NB <= 20) — 5 waves per SIMD instead of 4 at the 105
+// of the joint kernel.
 template <int NB, int K>
 __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
+    const int64_t* __restrict__ x_off, const int64_t* __restrict__ z_off, int n_shards,
+    int n_bags, PlanesPlan p, ClassPlan cp, const uint32_t* __restrict__ work,
+    unsigned long long* __restrict__ out) {
+  const int lb = xcd_block(blockIdx.x, gridDim.x);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int item = lb * (kBlock / kWave) + wid;
+  const int n_class = p.tiles_x * cp.cap;
+  const int v = item / n_class;
+  bool active = v < n_bags;
+  unsigned long long tot = 0;
+  if (active) {
+    const int s = v % n_shards;
+    const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
+    const int rem = item - v * n_class;
+    const int tx = rem / cp.cap, e = rem - tx * cp.cap;
+    const PlanesBag bag = planes_bag(nx, nz, p.swap != 0);
+    const int lim = bag.xgroups < p.gx ? bag.xgroups : p.gx;
+    const int g0 = tx * p.R;
+    const int ng = __builtin_amdgcn_readfirstlane(lim - g0 < p.R ? lim - g0 : p.R);
+    active = ng > 0 && e < (int)work[cp.off_cnt + v];
+    if (active) {
+      const uint32_t* __restrict__ tab = work + (cp.off_tab + ((int64_t)v * cp.cap + e) * 2);
+      const ClassRun r = class_entry((uint32_t)__builtin_amdgcn_readfirstlane((int)tab[0]),
+                                     (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[1]));
+      const uint32_t* __restrict__ pw =
+          work + bits_uniform(planes_word(NB, (int64_t)v * p.gx + g0, 0, 0));
+      const uint32_t* __restrict__ zs =
+          work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride + r.z0);
+      const int len = (int)r.len;  // >= 1: only non-empty classes have runs
+      unsigned long long t;
+      if (ng == 4)
+        t = bits_count_class<NB, K, 4>(pw, zs, len, r.cls, lane);
+      else if (ng == 3)
+        t = bits_count_class<NB, K, 3>(pw, zs, len, r.cls, lane);
+      else if (ng == 2)
+        t = bits_count_class<NB, K, 2>(pw, zs, len, r.cls, lane);
+      else
+        t = bits_count_class<NB, K, 1>(pw, zs, len, r.cls, lane);
+      tot = wave_sum_u64(t);
+    }
+  }
+  count_chain_epilogue(tot, active, v, wid, lane, out);
+}
+
+// The swapped items of a plan whose plane items went through class runs: per bag
+// p.tiles_s x p.schunks items, the x remainder as scalars against the bag's z planes, the
+// full-NB loop and the decode of k_count_chain_planes unchanged.  Adds to the same counts.
+template <int NB>
+__global__ __launch_bounds__(kBlock) void k_count_chain_swapped(
     const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
-    const int64_t* __restrict__ z_off, int n_shards, int n_bags, PlanesPlan p, ClassPlan cp,
+    const int64_t* __restrict__ z_off, int n_shards, int n_bags, PlanesPlan p,
     const uint32_t* __restrict__ work, unsigned long long* __restrict__ out) {
   const int lb = xcd_block(blockIdx.x, gridDim.x);
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int lane = threadIdx.x & (kWave - 1);
   const int item = lb * (kBlock / kWave) + wid;
-  const int v = item / cp.per_bag;
+  const int n_swapped = p.tiles_s * p.schunks;  // > 0: not launched otherwise
+  const int v = item / n_swapped;
   bool active = v < n_bags;
   unsigned long long tot = 0;
   if (active) {
     const int c = v / n_shards, s = v - c * n_shards;
     const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
-    const int rem = item - v * cp.per_bag;
-    const int n_class = p.tiles_x * cp.cap;
-    if (rem < n_class) {
-      const int tx = rem / cp.cap, e = rem - tx * cp.cap;
-      const PlanesBag bag = planes_bag(nx, nz, p.swap != 0);
-      const int lim = bag.xgroups < p.gx ? bag.xgroups : p.gx;
-      const int g0 = tx * p.R;
-      const int ng = __builtin_amdgcn_readfirstlane(lim - g0 < p.R ? lim - g0 : p.R);
-      active = ng > 0 && e < (int)work[cp.off_cnt + v];
-      if (active) {
-        const uint32_t* __restrict__ tab = work + (cp.off_tab + ((int64_t)v * cp.cap + e) * 2);
-        const ClassRun r = class_entry((uint32_t)__builtin_amdgcn_readfirstlane((int)tab[0]),
-                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[1]));
-        const uint32_t* __restrict__ pw =
-            work + bits_uniform(planes_word(NB, (int64_t)v * p.gx + g0, 0, 0));
-        const uint32_t* __restrict__ zs =
-            work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride + r.z0);
-        const int len = (int)r.len;  // >= 1: only non-empty classes have runs
-        unsigned long long t;
-        if (ng == 4)
-          t = bits_count_class<NB, K, 4>(pw, zs, len, r.cls, lane);
-        else if (ng == 3)
-          t = bits_count_class<NB, K, 3>(pw, zs, len, r.cls, lane);
-        else if (ng == 2)
-          t = bits_count_class<NB, K, 2>(pw, zs, len, r.cls, lane);
-        else
-          t = bits_count_class<NB, K, 1>(pw, zs, len, r.cls, lane);
-        tot = wave_sum_u64(t);
-      }
-    } else {
-      const PlanesItem it = planes_item(p, nx, nz, p.tiles_x * p.zchunks + (rem - n_class));
-      active = it.active;  // (swapped: rem past the plan's plane items)
-      if (active) {
-        const int64_t group = (int64_t)n_bags * p.gx + (int64_t)v * p.gz + it.g0;
-        const uint32_t* __restrict__ pw = work + bits_uniform(planes_word(NB, group, 0, 0));
-        const float* __restrict__ sf =
-            xb + bits_uniform((int64_t)c * x_stride + x_off[s] + it.s0);
-        const int ns = __builtin_amdgcn_readfirstlane((int)(it.s1 - it.s0));
-        const int ng = __builtin_amdgcn_readfirstlane(it.ng);
-        unsigned long long t;
-        if (ng == 4)
-          t = bits_count_planes<NB, 4>(pw, sf, ns, true, lane);
-        else if (ng == 3)
-          t = bits_count_planes<NB, 3>(pw, sf, ns, true, lane);
-        else if (ng == 2)
-          t = bits_count_planes<NB, 2>(pw, sf, ns, true, lane);
-        else
-          t = bits_count_planes<NB, 1>(pw, sf, ns, true, lane);
-        tot = wave_sum_u64(t);
-      }
+    const PlanesItem it =
+        planes_item(p, nx, nz, p.tiles_x * p.zchunks + (item - v * n_swapped));
+    active = it.active;  // (swapped: past the plan's plane items)
+    if (active) {
+      const int64_t group = (int64_t)n_bags * p.gx + (int64_t)v * p.gz + it.g0;
+      const uint32_t* __restrict__ pw = work + bits_uniform(planes_word(NB, group, 0, 0));
+      const float* __restrict__ sf = xb + bits_uniform((int64_t)c * x_stride + x_off[s] + it.s0);
+      const int ns = __builtin_amdgcn_readfirstlane((int)(it.s1 - it.s0));
+      const int ng = __builtin_amdgcn_readfirstlane(it.ng);
+      unsigned long long t;
+      if (ng == 4)
+        t = bits_count_planes<NB, 4>(pw, sf, ns, true, lane);
+      else if (ng == 3)
+        t = bits_count_planes<NB, 3>(pw, sf, ns, true, lane);
+      else if (ng == 2)
+        t = bits_count_planes<NB, 2>(pw, sf, ns, true, lane);
+      else
+        t = bits_count_planes<NB, 1>(pw, sf, ns, true, lane);
+      tot = wave_sum_u64(t);
     }
   }
   count_chain_epilogue(tot, active, v, wid, lane, out);
@@ -1465,7 +1488,8 @@ static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64
 }
 
 // The plane pre-pass and the count on its planes, back to back on st (out already zeroed);
-// with class bits (cp.k > 0) pre-pass 2 between them and the count on class runs
+// with class bits (cp.k > 0) pre-pass 2 between them, the plan's swapped items if it has any
+// and the count on class runs
 template <int NB>
 static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, const float* xb,
                                       const int64_t* d_x_off, int64_t x_stride, const float* zb,
@@ -1479,11 +1503,18 @@ static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, 
   if (cp.k > 0) {  // the class-run form: pre-pass 2, then the count on class runs
     hipLaunchKernelGGL(k_chain_zclasses, dim3((unsigned)bags), dim3(kBlock), 0, st, zb, d_z_off,
                        z_stride, n_shards, bags, NB, cp, work);
-    const dim3 g((unsigned)ceil_div((int64_t)bags * cp.per_bag, kBlock / kWave)), b(kBlock);
+    const int n_swapped = p.tiles_s * p.schunks;
+    if (n_swapped > 0)  // the plan's swapped items, in a launch of their own (same counts)
+      hipLaunchKernelGGL((k_count_chain_swapped<NB>),
+                         dim3((unsigned)ceil_div((int64_t)bags * n_swapped, kBlock / kWave)),
+                         dim3(kBlock), 0, st, xb, d_x_off, x_stride, d_z_off, n_shards, bags, p,
+                         (const uint32_t*)work, o);
+    const dim3 g((unsigned)ceil_div((int64_t)bags * p.tiles_x * cp.cap, kBlock / kWave)),
+        b(kBlock);
 #define TW_CLASS_CASE(K)                                                                       \
   case K:                                                                                      \
-    hipLaunchKernelGGL((k_count_chain_classes<NB, K>), g, b, 0, st, xb, d_x_off, x_stride,     \
-                       d_z_off, n_shards, bags, p, cp, (const uint32_t*)work, o);              \
+    hipLaunchKernelGGL((k_count_chain_classes<NB, K>), g, b, 0, st, d_x_off, d_z_off,          \
+                       n_shards, bags, p, cp, (const uint32_t*)work, o);                       \
     break;
     switch (cp.k) {
       TW_CLASS_CASE(1) TW_CLASS_CASE(2) TW_CLASS_CASE(3) TW_CLASS_CASE(4)
@@ -1523,12 +1554,14 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   if (nb == 0)
     return count_chain_launch(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride, n_shards,
                               steps, max_nx, max_nz, half, -1, d_out, st);
-  const PlanesPlan p = planes_plan(max_nx, max_nz, bags,
-                                   g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0,
-                                   g_chain_zchunk, g_planes_swap);
   // class bits: forced (clamped to this launch's planes), or chainclass.h's automatic rule
   const int k = g_class_bits < 0 ? class_bits_auto(max_nz, bags, nb)
                                  : std::min(g_class_bits, std::min(kClassMaxBits, nb - 8));
+  // (under class runs the automatic swap also asks which remainder costs fewer instructions)
+  const PlanesPlan p = planes_plan(max_nx, max_nz, bags,
+                                   g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0,
+                                   g_chain_zchunk,
+                                   class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k));
   const ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k);
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
                    bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&

@@ -19,6 +19,15 @@
 //  * a padded SCALAR slot is NOT harmless here — complemented 0 leaves c = 0 but counts G — so
 //    the class loop takes exactly the run's images and never evaluates a slot past its end.
 //
+// The class-constant term.  G is a subset of P, so with E = P & ~G — the x whose
+// top field EQUALS the class —
+//     popc(G | (P & c)) = popc(G) + popc(E & c):
+// popc(G) is the same for every z of a run and is counted once per item as len * popc(G), with
+// len the run's exact length.  E & c needs no instruction of its own: a slot whose low planes
+// are all 0 never carries from carry-in 0, so the low chain on the planes ANDed with E once per
+// item yields exactly E & c.  Per z and group the lane side is then NL + 1 (the chain and one
+// popcount).  Every pair still runs through its own low-bit chain.
+//
 // Everything here is plain C++ (host and device).
 #pragma once
 #include <stdint.h>
@@ -54,6 +63,26 @@ TW_BITS_HD void class_gp(const uint32_t (&top)[K], uint32_t D, uint32_t& G, uint
 template <int NL>
 TW_BITS_HD uint32_t class_gt32(const uint32_t (&low)[NL], uint32_t G, uint32_t P, uint32_t zc) {
   return bits_carry(G, P, bits_gt32<NL>(low, zc));
+}
+
+// E: the x of a group whose top field equals the class (G subset of P)
+TW_BITS_HD uint32_t class_equal_mask(uint32_t G, uint32_t P) { return P & ~G; }
+
+// The low planes of a group ANDed with E, once per item and group
+template <int NL>
+TW_BITS_HD void class_mask_planes(const uint32_t (&low)[NL], uint32_t E, uint32_t (&masked)[NL]) {
+#pragma unroll
+  for (int b = 0; b < NL; ++b) masked[b] = low[b] & E;
+}
+
+// The masked form of class_gt32: popc(class_gt32(low, G, P, zc)) == popc(constant) + popc(word)
+// with constant = G for every z of the class and word = E & c_low from the MASKED planes
+struct ClassMasked {
+  uint32_t constant, word;  // disjoint: G and a subset of E
+};
+template <int NL>
+TW_BITS_HD ClassMasked class_gt32_masked(const uint32_t (&masked)[NL], uint32_t G, uint32_t zc) {
+  return ClassMasked{G, bits_gt32<NL>(masked, zc)};
 }
 
 // ---------------------------------------------------------------------------- the run table
@@ -163,17 +192,63 @@ TW_BITS_HD int class_bits_auto(int64_t max_nz, int64_t n_bags, int nb) {
   return k;
 }
 
+// The swap mode a launch plans with (0 never, 1 chainplan.h's rule, 2 always) from the hook's
+// setting.  chainplan.h's automatic rule swaps the x remainder where it takes fewer SLOTS; under
+// class runs a padded slot costs NL + 1 VALU per z and group and a swapped one NB + 1.25, so the
+// automatic setting keeps the swap only where the swapped remainder of the largest bag is also
+// the cheaper in instructions: rx * ceil(nz / 2048) * (NB + 1.25) < nz * (NL + 1).  At the bench
+// shape (rx = 1289, nz = 15625, NB = 20, k = 8: 219 k against 203 k) that is no swap, measured
+// 0.93-0.95 of the swapped launch's time; a remainder of a few images stays
+// swapped.  Forced settings and launches without classes are left alone.
+TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb, int k) {
+  if (k == 0 || swap != 1) return swap;
+  const int64_t rx = max_nx % kPlaneGroup, zg = planes_ceil_div(max_nz, kPlaneGroup);
+  return rx * zg * (4 * nb + 5) < max_nz * 4 * (nb - k + 1) ? 1 : 0;
+}
+
 #if defined(__HIPCC__)
+// Build-time forms of the class loop (csrc/Makefile ab-classform):
+//   0  §4.1g's loop: bits_carry(G, P, c) per z, the images through a VGPR and v_readlane_b32
+//   1  masked low planes: the chain's carry is counted as it is, len * popc(G) once per item
+//   2  form 1 with the run read by scalar loads, TW_CLASS_BATCH images per load
+#ifndef TW_CLASS_FORM
+#define TW_CLASS_FORM 2
+#endif
+#ifndef TW_CLASS_BATCH
+#define TW_CLASS_BATCH 4
+#endif
+static_assert(TW_CLASS_FORM >= 0 && TW_CLASS_FORM <= 2, "TW_CLASS_FORM: 0, 1 or 2");
+static_assert(TW_CLASS_BATCH == 2 || TW_CLASS_BATCH == 4 || TW_CLASS_BATCH == 8 ||
+                  TW_CLASS_BATCH == 16,
+              "TW_CLASS_BATCH: a scalar load's width in words");
+// A scalar batch starts inside its run and may read up to TW_CLASS_BATCH - 1 words past the
+// run's end: into the same bag's later runs, the next bag's region or — from the last run of the
+// last bag — the entry counts, class_round64(n_bags) >= 64 words that follow the class-ordered
+// region (class_plan: off_cnt = off_zs + n_bags * zs_stride).  Always inside the workspace; the
+// words read past the end are never compared.
+static_assert(TW_CLASS_BATCH - 1 < 64, "the over-read must stay inside the count region");
+
 // One wave item: R groups of NB plane words per lane at pw (bits_count_planes' layout) against
-// the run's len >= 1 images at zs, complemented u32 of class cls (wave-uniform).  The images go
-// 64 at a time through one VGPR, the next 64 in flight, and reach the scalar side by
-// v_readlane_b32 as in bits_scalar_loop; two per trip, an odd last one in a step of its own.
+// the run's len >= 1 images at zs, complemented u32 of class cls (wave-uniform).  Exactly len
+// images are compared: a padded scalar slot would count G (form 0) or be missed by the
+// len * popc(G) term (forms 1, 2).
+//  Forms 0, 1: the images go 64 at a time through one VGPR, the next 64 in flight, and reach
+// the scalar side by v_readlane_b32 as in bits_scalar_loop; two per trip, an odd last one in a
+// step of its own.
+//  Form 2: zs is wave-uniform, so the run is read through the constant address space
+// (s_load_dwordxN straight into SGPRs): whole batches in an unrolled trip with the next batch
+// in flight, the last len mod TW_CLASS_BATCH images one at a time from the batch already loaded.
 template <int NB, int K, int R>
 __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* __restrict__ pw,
                                                                const uint32_t* __restrict__ zs,
                                                                int len, uint32_t cls, int lane) {
   constexpr int NL = NB - K;
-  uint32_t lo[R][NL], G[R], P[R], acc[R];
+  uint32_t lo[R][NL], acc[R];
+#if TW_CLASS_FORM == 0
+  uint32_t G[R], P[R];
+#else
+  uint32_t ng = 0;  // popc(G) over the groups: the class-constant term of one z
+#endif
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     uint32_t top[K];
@@ -181,7 +256,14 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
     for (int b = 0; b < NL; ++b) lo[r][b] = pw[(r * NB + b) * 64 + lane];
 #pragma unroll
     for (int b = 0; b < K; ++b) top[b] = pw[(r * NB + NL + b) * 64 + lane];
+#if TW_CLASS_FORM == 0
     class_gp<K>(top, cls, G[r], P[r]);
+#else
+    uint32_t g, p;
+    class_gp<K>(top, cls, g, p);
+    class_mask_planes<NL>(lo[r], class_equal_mask(g, p), lo[r]);
+    ng = bits_popc_add(g, ng);
+#endif
     acc[r] = 0;
   }
   auto step = [&](uint32_t sc) {
@@ -195,8 +277,37 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
 #pragma unroll
       for (int r = 0; r < R; ++r) c[r] = bits_carry(lo[r][b], m[b], c[r]);
 #pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = bits_popc_add(bits_carry(G[r], P[r], c[r]), acc[r]);
+    for (int r = 0; r < R; ++r)
+#if TW_CLASS_FORM == 0
+      acc[r] = bits_popc_add(bits_carry(G[r], P[r], c[r]), acc[r]);
+#else
+      acc[r] = bits_popc_add(c[r], acc[r]);
+#endif
   };
+#if TW_CLASS_FORM == 2
+  constexpr int B = TW_CLASS_BATCH;
+  typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+  const ConstWords zc = (ConstWords)(uintptr_t)zs;
+  uint32_t cur[B], next[B];
+  auto load = [&](int j, uint32_t (&w)[B]) {
+#pragma unroll
+    for (int u = 0; u < B; ++u) w[u] = zc[j + u];
+  };
+  load(0, next);
+  int j = 0;
+  for (; j + B <= len; j += B) {
+#pragma unroll
+    for (int u = 0; u < B; ++u) cur[u] = next[u];
+    load(min(j + B, len - 1), next);  // (starts inside the run; past a last whole batch: unused)
+#pragma unroll
+    for (int u = 0; u < B; ++u) step(cur[u]);
+  }
+  for (; j < len; ++j) {  // next holds the images from j on: never a word past the run's end
+    step(next[0]);
+#pragma unroll
+    for (int u = 0; u + 1 < B; ++u) next[u] = next[u + 1];
+  }
+#else
   auto load = [&](int j) -> uint32_t { return zs[min(j + lane, len - 1)]; };  // (no branch)
   uint32_t next = load(0);
   for (int j = 0; j < len; j += 64) {
@@ -210,9 +321,13 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
     }
     if (l < cnt) step((uint32_t)__builtin_amdgcn_readlane((int)sv, l));  // never a padded slot
   }
+#endif
   unsigned long long tot = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) tot += acc[r];
+#if TW_CLASS_FORM != 0
+  tot += (unsigned long long)(uint32_t)len * ng;  // the run's exact length
+#endif
   return tot;
 }
 #endif  // __HIPCC__
