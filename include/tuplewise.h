@@ -1151,6 +1151,32 @@ int tw_self_pairs_idx32(const void* d_s, const int32_t* d_i, const int32_t* d_j,
                         const int64_t* d_pair_off, int32_t n_shards, int64_t max_pairs,
                         int32_t dtype, int32_t kern, void* d_work, void* d_out, void* stream);
 
+/* ---- The same numbers for ONE large sample without walking its pairs (csrc/selfsorted.hip;
+ * DESIGN.md §4.9b): chunk sorts and binary searches in every sorted chunk, O(n (n / chunk) log
+ * chunk) per pass.  d_s, d_off, dtype and d_out are tw_self_pairs'; total_n >= d_off[n_shards] -
+ * d_off[0] sizes the scratch, max_n <= 2^31 - 1 is the largest shard.
+ *   TW_SELF_KENDALL  (TW_F64, TW_I64) the five uint64 C, D, Tx, Ty, Txy — exactly the integers of
+ *                    tw_self_pairs on every input (NaN, -0.0, +-inf, INT64_MAX included): D is
+ *                    the number of strict inversions of b over the points with no NaN sorted by
+ *                    (a, b), C = v (v - 1) / 2 - Tx' - Ty' + Txy - D over those v points;
+ *   TW_SELF_GINI     (TW_F64) sum_i (2 i - n + 1) s_(i) over the sorted shard: exact
+ *                    two-products summed in double-double in a fixed order and rounded once, so
+ *                    a shard's double has the same bits alone or beside other shards (it differs
+ *                    from tw_self_pairs' blocked sum in the last bits).  NaN if the shard holds
+ *                    a NaN, two +inf or two -inf, else +inf if it holds an infinity;
+ *   TW_SELF_VAR      refused (TW_ERR_ARG): the variance is O(n) from the moments.
+ * chunk: 0 for tw_self_sorted_chunk(), or a power of two in [1024, 16384] keys.  The Kendall
+ * integers do not depend on it; the Gini double is summed in another order under another chunk
+ * (each within an ulp of the exact sum).  The input is not modified; d_work holds
+ * tw_self_sorted_work_bytes(...) bytes; everything is ordered on `stream`.  Argument errors
+ * return TW_ERR_ARG before any launch. */
+int64_t tw_self_sorted_work_bytes(int32_t n_shards, int64_t total_n, int64_t max_n, int32_t kern,
+                                  int32_t chunk);
+int32_t tw_self_sorted_chunk(void);
+int tw_self_sorted(const void* d_s, const int64_t* d_off, int32_t n_shards, int64_t total_n,
+                   int64_t max_n, int32_t dtype, int32_t kern, int32_t chunk, void* d_work,
+                   void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,16 @@ np.var(ddof=1), and a chunked NumPy all-pairs sum for Gini.
 Kendall's rate is set against the VALU peak 3.93e13 lane-op/s divided by the inner loop's own
 lane-ops per pair (--kendall-lane-ops, counted in the ISA: DESIGN.md §4.9).
 
-Usage: time_onesample.py [--out profiles/time_onesample.json] [--quick]"""
+--sorted: the sorted path (tw_self_sorted, csrc/selfsorted.hip) beside all pairs, same method:
+Kendall and Gini Un at n = 1e4, 1e5, 1e6 with both algorithms and at 1e7 sorted only (the
+all-pairs figure there is extrapolated from its pairs/s at 1e6 and marked so), the UnN shape
+n = 1e6, N = 64 with both, and the chunk sweep at 1e6; writes profiles/time_onesample_sorted.json.
+The split of the sorted Kendall time over its launches comes from a kernel trace of its own:
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o run -- \\
+        python tools/time_onesample.py --trace-sorted 1000000
+    python tools/time_onesample.py --trace-sorted 1000000 --split-from OUT/.../run_kernel_stats.csv
+
+Usage: time_onesample.py [--out profiles/time_onesample.json] [--quick] [--sorted]"""
 import argparse
 import json
 import os
@@ -122,14 +131,145 @@ def host_reference(S, kernel):
     return "chunked NumPy all-pairs", lambda: gini_host(S)
 
 
+def sorted_launch(S, blocks, k, kernel, chunk=0):
+    """A closure launching tw_self_sorted on `blocks` resident blocks of k items of S."""
+    ken = kernel == "kendall"
+    sd = L.to_device(S.reshape(-1))
+    od = L.to_device(np.arange(blocks + 1, dtype=np.int64) * k)
+    need = L.lib().tw_self_sorted_work_bytes(blocks, blocks * k, k, CODES[kernel], chunk)
+    work = L.empty((need // 8,), torch.int64)
+    out = L.empty((blocks, 5 if ken else 1), torch.int64 if ken else torch.float64)
+
+    def go():
+        L.call("tw_self_sorted", sd, od, blocks, blocks * k, k, L.TW_F64, CODES[kernel], chunk,
+               work, out, L.stream_handle())
+    return go, out
+
+
+def same_result(a, b, kernel):
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    if kernel == "kendall":
+        return bool(np.array_equal(a, b))
+    return bool(np.allclose(a, b, rtol=1e-12, atol=0.0))
+
+
+def phase_of(kernel_name):
+    """The phase of tw_self_sorted's Kendall path a kernel belongs to (csrc/selfsorted.hip)."""
+    head = kernel_name.split("(")[0]
+    if "k_ss_sort_vals" in head or "k_ss_count" in head or "k_ss_compose" in head:
+        return "ranks"
+    if "k_ss_order" in head or ("k_ss_sort_keys" in head and "false" in head):
+        return "order"
+    if "k_ss_cross" in head or "k_ss_sort_keys" in head:
+        return "inversions"
+    if "k_ss_final_kendall" in head or "tw::k_zero_fill" in head:
+        return "rest"
+    return None
+
+
+def split_from(csv_path, calls):
+    """Device time of one tw_self_sorted call by phase, from the kernel stats of a rocprofv3
+    --kernel-trace --stats run of `--trace-sorted` (`calls` launches of the entry point)."""
+    import csv
+    phases = {"ranks": 0.0, "order": 0.0, "inversions": 0.0, "rest": 0.0}
+    kernels = {}
+    with open(csv_path, newline="") as f:
+        for row in csv.DictReader(f):
+            phase = phase_of(row["Name"])
+            if phase:
+                ms = float(row["TotalDurationNs"]) * 1e-6 / calls
+                phases[phase] += ms
+                kernels[row["Name"].split("(")[0].replace("void tw::", "")] = ms
+    return {"ms_per_call": phases, "kernels_ms_per_call": kernels, "calls": calls}
+
+
+def sorted_table(a):
+    """The sorted path beside all pairs: Un of Kendall and Gini at n = 1e4 .. 1e7 (all pairs at
+    1e7 extrapolated from its pairs/s at 1e6), the UnN shape, and the chunk sweep at 1e6."""
+    sizes = (2_000, 20_000) if a.quick else (10_000, 100_000, 1_000_000, 10_000_000)
+    n2, N = (100_000, 64) if a.quick else (1_000_000, 64)
+    res = {"device": torch.cuda.get_device_name(0),
+           "chunk": int(L.lib().tw_self_sorted_chunk()),
+           "timing": "device events, median of 5 windows of `reps` launches after a warm call, "
+                     "ms per launch, resident operands",
+           "rows": [], "chunk_sweep": []}
+    for kernel in ("kendall", "gini"):
+        rate = None
+        for n in sizes:
+            S = make(n, kernel, 1)
+            pairs = n * (n - 1) // 2
+            go_s, out_s = sorted_launch(S, 1, n, kernel)
+            row = {"shape": f"Un n={n}", "kernel": kernel, "pairs": pairs,
+                   "sorted_ms": device_ms(go_s, 20 if n <= 100_000 else 3 if n <= 1_000_000 else 1)}
+            if n <= 1_000_000:
+                go_p, out_p = complete_launch(S, 1, n, kernel)
+                row["pairs_ms"] = device_ms(go_p, 20 if n <= 100_000 else 1)
+                row["same_result"] = same_result(out_s, out_p, kernel)
+                rate = pairs / row["pairs_ms"]
+            else:
+                row["pairs_ms_extrapolated"] = pairs / rate  # at the pairs/s of the size before
+            row["speedup"] = row.get("pairs_ms", row.get("pairs_ms_extrapolated")) / row["sorted_ms"]
+            print(json.dumps(row), flush=True)
+            res["rows"].append(row)
+            del go_s, out_s
+            torch.cuda.empty_cache()
+        S = make(n2, kernel, 2)
+        k = n2 // N
+        go_s, out_s = sorted_launch(S, N, k, kernel)
+        go_p, out_p = complete_launch(S, N, k, kernel)
+        row = {"shape": f"UnN n={n2} N={N}", "kernel": kernel, "pairs": N * (k * (k - 1) // 2),
+               "sorted_ms": device_ms(go_s, 5), "pairs_ms": device_ms(go_p, 5)}
+        row["same_result"] = same_result(out_s, out_p, kernel)
+        row["speedup"] = row["pairs_ms"] / row["sorted_ms"]
+        print(json.dumps(row), flush=True)
+        res["rows"].append(row)
+    n = sizes[-2]
+    S = make(n, "kendall", 1)
+    for chunk in (1024, 2048, 4096, 8192, 16384):
+        go_s, _ = sorted_launch(S, 1, n, "kendall", chunk)
+        row = {"shape": f"Un n={n}", "kernel": "kendall", "chunk": chunk,
+               "sorted_ms": device_ms(go_s, 3)}
+        print(json.dumps(row), flush=True)
+        res["chunk_sweep"].append(row)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "time_onesample.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="n = 2e4 / 1e5 instead of 1e5 / 1e6")
     ap.add_argument("--kendall-lane-ops", type=float, default=11.75,
                     help="VALU instructions per pair of the Kendall inner loop (from the ISA)")
+    ap.add_argument("--sorted", action="store_true",
+                    help="the sorted path beside all pairs (profiles/time_onesample_sorted.json)")
+    ap.add_argument("--trace-sorted", type=int, default=0, metavar="N",
+                    help="only launch the sorted Kendall count of N points --calls times: the "
+                         "program of a rocprofv3 --kernel-trace --stats run")
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--split-from", default=None, metavar="CSV",
+                    help="add the per-phase split from that run's kernel stats to --out")
     a = ap.parse_args()
+    sorted_out = a.out or str(ROOT / "profiles" / "time_onesample_sorted.json")
+    if a.split_from:
+        res = json.loads(pathlib.Path(sorted_out).read_text())
+        res["split"] = dict(split_from(a.split_from, a.calls), n=a.trace_sorted)
+        pathlib.Path(sorted_out).write_text(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res["split"]))
+        return
     torch.cuda.set_device(0)
+    if a.trace_sorted:
+        go, _ = sorted_launch(make(a.trace_sorted, "kendall", 1), 1, a.trace_sorted, "kendall")
+        for _ in range(a.calls):
+            go()
+        torch.cuda.synchronize()
+        return
+    if a.sorted:
+        res = sorted_table(a)
+        out = pathlib.Path(sorted_out)
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps(res, indent=1) + "\n")
+        return
+    a.out = a.out or str(ROOT / "profiles" / "time_onesample.json")
     if hasattr(os, "sched_setaffinity"):  # the host comparisons on one core
         os.sched_setaffinity(0, {sorted(os.sched_getaffinity(0))[0]})
     torch.set_num_threads(1)

@@ -247,6 +247,9 @@ _SIGNATURES = {
     "tw_self_pairs_tile": [],
     "tw_self_pairs": [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp],
     "tw_self_pairs_idx32": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp],
+    "tw_self_sorted_work_bytes": [_i32, _i64, _i64, _i32, _i32],
+    "tw_self_sorted_chunk": [],
+    "tw_self_sorted": [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -266,6 +269,7 @@ _RESTYPES = {
     "tw_np_randint_dev_work_bytes": ctypes.c_int64,
     "tw_self_pairs_work_bytes": ctypes.c_int64,
     "tw_self_pairs_idx_work_bytes": ctypes.c_int64,
+    "tw_self_sorted_work_bytes": ctypes.c_int64,
     "tw_chain_planes_work_bytes": ctypes.c_int64,
 }
 

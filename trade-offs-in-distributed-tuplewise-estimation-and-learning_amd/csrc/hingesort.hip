@@ -29,48 +29,16 @@
 //                               per x the predicate search, the top-c sum, double-double
 //                               accumulation, block reduction -> one partial; x counts
 //   k_hs_final                  per shard: partials in tile order, the non-finite rules
+#include "ddmath.h"
 #include "sortkeys.h"
 #include <algorithm>
 
 namespace tw {
 
-constexpr int kHsC = 4096;       // z per sorted chunk: 32 KiB of keys + 64 KiB of P in LDS
+constexpr int kHsC = 4096;      // z per sorted chunk: 32 KiB of keys + 64 KiB of P in LDS
 constexpr int kHsThreads = 1024;
 constexpr int kHsXPer = 4;       // x values per thread
 constexpr int kHsCounts = 8;     // per shard: x NaN, x +inf, x -inf, z NaN, z +inf, z -inf
-
-struct ddv {
-  double hi, lo;
-};
-__device__ __forceinline__ ddv two_sum(double a, double b) {
-  const double s = a + b;
-  const double bb = s - a;
-  return {s, (a - (s - bb)) + (b - bb)};
-}
-__device__ __forceinline__ ddv quick_two_sum(double a, double b) {
-  const double s = a + b;
-  return {s, b - (s - a)};
-}
-__device__ __forceinline__ ddv dd_add(ddv a, ddv b) {
-  ddv s = two_sum(a.hi, b.hi);
-  const ddv t = two_sum(a.lo, b.lo);
-  s.lo += t.hi;
-  s = quick_two_sum(s.hi, s.lo);
-  s.lo += t.lo;
-  return quick_two_sum(s.hi, s.lo);
-}
-__device__ __forceinline__ ddv dd_neg(ddv a) { return {-a.hi, -a.lo}; }
-// a * c for an exact small integer c (as a double)
-__device__ __forceinline__ ddv dd_mul_d(ddv a, double c) {
-  const double p = a.hi * c;
-  const double e = __fma_rn(a.hi, c, -p);
-  return quick_two_sum(p, e + a.lo * c);
-}
-__device__ __forceinline__ ddv dd_shfl_xor(ddv a, int m) {
-  return {__shfl_xor(a.hi, m, kWave), __shfl_xor(a.lo, m, kWave)};
-}
-
-__device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
 
 // per chunk: P[k] = sum of the chunk's first k sorted values (non-finite, NaN and padding as 0)
 __global__ __launch_bounds__(kHsThreads) void k_hs_prefix(const uint64_t* __restrict__ sorted,

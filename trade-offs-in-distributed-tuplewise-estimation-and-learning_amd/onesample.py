@@ -20,6 +20,13 @@ sample: UN shuffles the caller's array in place, cuts N blocks of k = int(n / N)
 remainder is left out, as prop-SWOR does) and averages the block values; all blocks of a block
 function made here run in ONE launch of csrc/selfpairs.hip.  Only the partition without
 replacement is offered (DESIGN.md §4.9 lists what is out of scope).
+
+algo= chooses how the complete statistics are evaluated: "pairs" walks all n (n - 1) / 2 pairs
+(csrc/selfpairs.hip), "sorted" sorts and searches (csrc/selfsorted.hip, DESIGN.md §4.9b: "gini"
+and "kendall"), "auto" takes the sorted path once the largest shard has SORTED_MIN_N points.
+Kendall's integers are the same either way, so its default is "auto"; the sorted Gini sum is
+rounded once instead of block by block and differs in the last bits, so "gini" stays on "pairs"
+unless asked.
 """
 from __future__ import annotations
 
@@ -33,6 +40,10 @@ from .numpy_rng import randint_batch
 
 _KERNELS = ["gini", "var", "kendall"]
 _CODES = {"gini": L.TW_SELF_GINI, "var": L.TW_SELF_VAR, "kendall": L.TW_SELF_KENDALL}
+_ALGOS = ["pairs", "sorted", "auto"]
+# "auto": the largest shard's size from which the sorted path is taken (the smallest measured n
+# at which it beats all pairs for one shard: tools/time_onesample.py)
+SORTED_MIN_N = 100_000
 
 
 # ------------------------------------------------------------------------------ host checks
@@ -57,6 +68,27 @@ def _items(S, kernel):
     return S, S.shape[0], L.TW_F64
 
 
+def _check_algo(kernel, algo):
+    """algo= as given by the caller (None: the kernel's default).  Raises before anything else
+    happens."""
+    if algo is None:
+        return "auto" if kernel == "kendall" else "pairs"
+    if algo not in _ALGOS:
+        raise ValueError(f"algo={algo!r} is not one of {_ALGOS}")
+    if algo == "sorted" and kernel == "var":
+        raise ValueError("kernel='var' has no sorted path (np.var is the O(n) tool); use "
+                         "algo='pairs'")
+    return algo
+
+
+def _choose_algo(kernel, algo, max_n) -> str:
+    """"pairs" or "sorted" for a launch whose largest shard has max_n items."""
+    algo = _check_algo(kernel, algo)
+    if algo == "auto":
+        return "sorted" if kernel != "var" and max_n >= SORTED_MIN_N else "pairs"
+    return algo
+
+
 def _need_pairs(n, what="sample"):
     if n < 2:
         raise ValueError(f"a {what} of {n} point(s) has no pairs (at least 2 are needed)")
@@ -76,20 +108,27 @@ def _float_mean(total, pairs: int) -> np.float64:
 
 
 # ------------------------------------------------------------------------------ device glue
-def _launch_complete(flat, off, code, kernel):
-    """tw_self_pairs on one upload of (sample, item offsets): the (n_shards, 1) float64 sums or
-    the (n_shards, 5) uint64 Kendall counters, on the host."""
+def _launch_complete(flat, off, code, kernel, algo=None):
+    """tw_self_pairs or tw_self_sorted (_choose_algo) on one upload of (sample, item offsets): the
+    (n_shards, 1) float64 sums or the (n_shards, 5) uint64 Kendall counters, on the host."""
     t = L.torch()
     L.device()  # no HIP device: the package's RuntimeError, before any native call
     n_shards = len(off) - 1
     sd, od = L.to_device_many([flat, off])
     max_n = int(np.diff(off).max()) if n_shards else 0
-    work = L.empty((max(1, int(L.lib().tw_self_pairs_work_bytes(n_shards, max_n)) // 8),),
-                   t.int64)
     ken = kernel == "kendall"
     out = L.empty((n_shards, 5 if ken else 1), t.int64 if ken else t.float64)
-    L.call("tw_self_pairs", sd, od, n_shards, max_n, code, _CODES[kernel], work, out,
-           L.stream_handle())
+    if _choose_algo(kernel, algo, max_n) == "sorted":
+        total = int(off[-1] - off[0])
+        need = L.lib().tw_self_sorted_work_bytes(n_shards, total, max_n, _CODES[kernel], 0)
+        work = L.empty((max(1, int(need) // 8),), t.int64)
+        L.call("tw_self_sorted", sd, od, n_shards, total, max_n, code, _CODES[kernel], 0, work,
+               out, L.stream_handle())
+    else:
+        work = L.empty((max(1, int(L.lib().tw_self_pairs_work_bytes(n_shards, max_n)) // 8),),
+                       t.int64)
+        L.call("tw_self_pairs", sd, od, n_shards, max_n, code, _CODES[kernel], work, out,
+               L.stream_handle())
     host = out.cpu().numpy()
     return host.view(np.uint64) if ken else host
 
@@ -123,27 +162,29 @@ def _values(raw, pairs, kernel):
 
 
 # ------------------------------------------------------------------------------- estimators
-def Un(S, kernel="gini"):
+def Un(S, kernel="gini", algo=None):
     """The complete one-sample U-statistic: the mean of h over all pairs i < j."""
     assert kernel in _KERNELS
+    algo = _check_algo(kernel, algo)
     flat, n, code = _items(S, kernel)
     _need_pairs(n)
-    raw = _launch_complete(flat, np.array([0, n], dtype=np.int64), code, kernel)
+    raw = _launch_complete(flat, np.array([0, n], dtype=np.int64), code, kernel, algo)
     return _values(raw, [_pairs(n)], kernel)[0]
 
 
-def kendall_counts(S):
+def kendall_counts(S, algo=None):
     """(C, D, Tx, Ty, Txy) over all pairs of the (n, 2) sample, as Python ints."""
+    algo = _check_algo("kendall", algo)
     flat, n, code = _items(S, "kendall")
     _need_pairs(n)
-    raw = _launch_complete(flat, np.array([0, n], dtype=np.int64), code, "kendall")
+    raw = _launch_complete(flat, np.array([0, n], dtype=np.int64), code, "kendall", algo)
     return tuple(int(v) for v in raw[0])
 
 
-def kendall_tau_b(S):
+def kendall_tau_b(S, algo=None):
     """(C - D) / (sqrt(P - Tx) * sqrt(P - Ty)); NaN when a factor is 0 (one coordinate is
     constant)."""
-    c, d, tx, ty, _ = kendall_counts(S)
+    c, d, tx, ty, _ = kendall_counts(S, algo)
     p = _pairs(np.asarray(S).shape[0])
     fx, fy = math.sqrt(float(p - tx)), math.sqrt(float(p - ty))
     if fx == 0.0 or fy == 0.0:
@@ -194,15 +235,15 @@ def UB(S, B, kernel="gini"):
 class _Complete:
     """Tag of a block function made by UnN: every block's Un."""
 
-    def __init__(self, kernel):
-        self.kernel = kernel
+    def __init__(self, kernel, algo=None):
+        self.kernel, self.algo = kernel, _check_algo(kernel, algo)
 
     def draw(self, k, N):
         return None
 
     def evaluate(self, flat, code, k, blocks, draws):
         off = np.arange(blocks + 1, dtype=np.int64) * k
-        raw = _launch_complete(flat, off, code, self.kernel)
+        raw = _launch_complete(flat, off, code, self.kernel, self.algo)
         return _values(raw, [_pairs(k)] * blocks, self.kernel)
 
 
@@ -279,10 +320,10 @@ def UN(S, N, f_block):
 Un._tw_self_block = _Complete("gini")  # UN(S, N, Un): Un's default kernel on every block
 
 
-def _complete_block(kernel):
+def _complete_block(kernel, algo=None):
     def fun_block(s):
-        return Un(s, kernel=kernel)
-    return _block_fn(_Complete(kernel), fun_block)
+        return Un(s, kernel=kernel, algo=algo)
+    return _block_fn(_Complete(kernel, algo), fun_block)
 
 
 def _incomplete_block(B, kernel):
@@ -291,10 +332,10 @@ def _incomplete_block(B, kernel):
     return _block_fn(_Incomplete(B, kernel), fun_block)
 
 
-def UnN(S, N, kernel="gini"):
+def UnN(S, N, kernel="gini", algo=None):
     """Block-wise complete one-sample U-statistic."""
     assert kernel in _KERNELS
-    return UN(S, N, _complete_block(kernel))
+    return UN(S, N, _complete_block(kernel, algo))
 
 
 def UnNB(S, N, B, kernel="gini"):
@@ -303,11 +344,11 @@ def UnNB(S, N, B, kernel="gini"):
     return UN(S, N, _incomplete_block(B, kernel))
 
 
-def UnNT(S, N, T, kernel="gini"):
+def UnNT(S, N, T, kernel="gini", algo=None):
     """Reshuffled block-wise complete U-statistic: np.mean of T UnN calls, the T x N blocks in
     one launch."""
     assert kernel in _KERNELS
-    return _run(S, N, _Complete(kernel), T)
+    return _run(S, N, _Complete(kernel, algo), T)
 
 
 def UnNBT(S, N, B, T, kernel="gini"):
