@@ -227,6 +227,10 @@ int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off, int
  * tables), sized for any plan and any class bits, so the tuning hooks do not change it. */
 int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
                                    int64_t max_nz, int32_t half, int64_t image_bound);
+/* The form of the class loop a count with nb planes and k class bits runs in this build
+ * (DESIGN §4.1h, §4.1i): 3 = the digit tables, where nb - k low planes fit them; 2 = masked
+ * planes and scalar loads; 0, 1 in A/B builds only.  A query: there is no hook to set it. */
+int32_t tw_count_chain_class_form(int32_t nb, int32_t k);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
  * estimation-experiment/main.py:29-31's integer): each bag's z images (integers in
  * [0, z_total], z_total = the Z count the images were ranked against) counting-sorted into

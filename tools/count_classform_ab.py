@@ -1,6 +1,6 @@
-"""A/B of the class loop's build-time forms (csrc/chainclass.h TW_CLASS_FORM / TW_CLASS_BATCH,
-DESIGN §4.1h) on tools/count_classes_ab.py's shapes.  One fresh child process per variant
-library (`make -C <pkg>/csrc ab-classform` -> tools/variants/libtuplewise_classform*.so, chosen
+"""A/B of the class loop's build-time forms (csrc/chainclass.h TW_CLASS_FORM / TW_CLASS_BATCH /
+TW_CLASS_DIGIT_R) on tools/count_classes_ab.py's shapes.  One fresh child
+process per variant library (`make -C <pkg>/csrc ab-classform` -> tools/variants/libtuplewise_classform*.so, chosen
 with TW_LIB_PATH; "product" is the library as built), the children alternated over REPS passes.
 Inside each child, tw_count_pairs_chain_planes with classes off (tw_count_chain_set_class_bits
 0: k_count_chain_planes, which no form touches — the in-process yardstick), under the automatic
@@ -10,7 +10,8 @@ interleaved over 7 rounds; per setting the median, min and max ms of the whole n
 (both pre-passes + count) and the ratio of medians to k = 0 of the same process.  Counts must
 agree exactly.
 Run on the GPU box:  python tools/count_classform_ab.py [out.json [variant ...]]
-(variants by file suffix, e.g. classform1 classform2b16; default: every library present)"""
+(variants by file suffix, e.g. classform1 classform2b16 classform3r2 — form 3, the digit
+tables, with R groups per item; default: every library present)"""
 import json
 import os
 import pathlib

@@ -654,7 +654,8 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_planes(
 // table is written: per non-empty class ceil(n_c / cp.chunk) runs of near-equal length.  Two
 // passes over the images in global memory (histogram; scatter through LDS cursors), so a bag
 // of any size goes through; the order inside a class is that of the cursors' atomics, which
-// the counts — integer sums — do not see.
+// the counts — integer sums — do not see.  With cp.digits > 0 (the digit loop)
+// an image is stored digit-ready (class_digit_encode): one word per image either way.
 __device__ __forceinline__ uint32_t class_block_scan(uint32_t v, uint32_t* wsum, int lane,
                                                      int wid) {
 #pragma unroll
@@ -714,7 +715,8 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
     for (int u = 0; u < U; ++u) {
       const uint32_t zc = bits_z_image(f[u]);
       if (i0 + u * kBlock < nz)
-        zs[atomicAdd(&hist[class_of(zc, nb, cp.k)], 1u)] = zc;  // < c0 + n <= nz
+        zs[atomicAdd(&hist[class_of(zc, nb, cp.k)], 1u)] =  // < c0 + n <= nz
+            cp.digits > 0 ? class_digit_encode(zc, cp.digits) : zc;
     }
   }
 }
@@ -725,7 +727,9 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
 // len images.  The plan's swapped items run in a launch of their own (k_count_chain_swapped):
 // their full-NB loop holds R * NB planes per lane, and without it this kernel allocates 89
 // VGPRs at NB = 20, k = 8 (at most 94 at NB <= 20) — 5 waves per SIMD instead of 4 at the 105
-// of the joint kernel.
+// of the joint kernel.  Where the low field fits the digit tables (form 3, DESIGN
+// §4.1i) the run's images are digit-ready and the item runs bits_count_class_digits: about
+// 100 VGPRs, 4 waves.
 template <int NB, int K>
 __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
     const int64_t* __restrict__ x_off, const int64_t* __restrict__ z_off, int n_shards,
@@ -759,6 +763,12 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
           work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride + r.z0);
       const int len = (int)r.len;  // >= 1: only non-empty classes have runs
       unsigned long long t;
+#if TW_CLASS_FORM == 3
+      if constexpr (class_loop_form(NB, K) == 3) {  // the digit loop: the launcher planned
+        t = bits_count_class_digits_of<NB, K, kClassDigitsMaxR>(  // R <= kClassDigitsMaxR
+            pw, zs, len, r.cls, lane, ng);
+      } else
+#endif
       if (ng == 4)
         t = bits_count_class<NB, K, 4>(pw, zs, len, r.cls, lane);
       else if (ng == 3)
@@ -1558,11 +1568,14 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   const int k = g_class_bits < 0 ? class_bits_auto(max_nz, bags, nb)
                                  : std::min(g_class_bits, std::min(kClassMaxBits, nb - 8));
   // (under class runs the automatic swap also asks which remainder costs fewer instructions)
-  const PlanesPlan p = planes_plan(max_nx, max_nz, bags,
-                                   g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0,
-                                   g_chain_zchunk,
+  // The digit loop's register map holds kClassDigitsMaxR groups: the plan's tiles follow
+  const bool digits = k > 0 && class_loop_form(nb, k) == 3;
+  int R = g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0;
+  if (digits) R = R == 0 || R > kClassDigitsMaxR ? kClassDigitsMaxR : R;
+  const PlanesPlan p = planes_plan(max_nx, max_nz, bags, R, g_chain_zchunk,
                                    class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k));
-  const ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k);
+  ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k);
+  cp.digits = digits ? nb - k : 0;
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
                    bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&
                    bags * (int64_t)cp.per_bag < (1ll << 31),
@@ -1590,6 +1603,12 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   return TW_OK;
 }
 }  // namespace tw
+
+// The loop form the class count of a launch with nb planes and k class bits runs in this build
+// (chainclass.h TW_CLASS_FORM; 3: the digit tables, where the low field fits them)
+extern "C" int32_t tw_count_chain_class_form(int32_t nb, int32_t k) {
+  return class_loop_form(nb, k);
+}
 
 extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
                                               int64_t max_nz, int32_t half,

@@ -85,6 +85,116 @@ TW_BITS_HD ClassMasked class_gt32_masked(const uint32_t (&masked)[NL], uint32_t 
   return ClassMasked{G, bits_gt32<NL>(masked, zc)};
 }
 
+// ------------------------------------------------------------------------- the digit tables
+// The low chain by table lookup.  The NL low planes are cut into kClassDigits
+// DIGITS of at most kClassDigitBits planes, digit 0 the lowest.  For each of the 2^w values d a
+// z image's digit can take, the carry through the digit is majority(G_d, P_d, c) with
+//     G_d = the digit's own chain with carry-in 0,   P_d = the same chain with carry-in ones
+// — class_gp's arithmetic on w planes — and G_d, P_d depend on the x planes and d alone: they
+// are built once per item and group and the per-z chain is one step per DIGIT, its operands
+// chosen by d.  G_d is the carry out of x_digit + d, so a carry-in of one is one more in d:
+//     P_d = G_(d+1),   G_0 = 0,   G_(2^w) = ones,
+// and one table of 2^w + 1 entries serves both: the step reads entries d and d + 1.  Digit 0 has
+// carry-in 0: its step is c = G_d and it needs no entry 2^w.  The top digit's planes are ANDed
+// with E and its entry 2^w is E, which makes its entries G_d & E: the chain yields E & c,
+// class_gt32_masked's word.
+constexpr int kClassDigits = 4;     // digits of the low field, whatever its width
+constexpr int kClassDigitBits = 3;  // widest digit: tables of 2^3 (+ 1) entries
+constexpr int kClassDigitMaxNL = kClassDigits * kClassDigitBits;
+constexpr int kClassDigitEntries = (1 << kClassDigitBits) + 1;
+
+// The split: NL / 4 planes each, the NL mod 4 lowest digits one more (12: 3,3,3,3; 11:
+// 3,3,3,2; 10: 3,3,2,2; 9: 3,2,2,2; 8: 2,2,2,2)
+constexpr int class_digit_width(int nl, int j) {
+  return nl / kClassDigits + (j < nl % kClassDigits ? 1 : 0);
+}
+constexpr int class_digit_shift(int nl, int j) {
+  int s = 0;
+  for (int i = 0; i < j; ++i) s += class_digit_width(nl, i);
+  return s;
+}
+// a low field the tables take: every digit has 1 .. kClassDigitBits planes
+constexpr bool class_digits_fit(int nl) { return nl >= kClassDigits && nl <= kClassDigitMaxNL; }
+// table entries (VGPRs per lane and group) the split uses: 2^w of digit 0, 2^w + 1 of the others
+constexpr int class_digit_table_regs(int nl) {
+  int n = 1 << class_digit_width(nl, 0);
+  for (int j = 1; j < kClassDigits; ++j) n += (1 << class_digit_width(nl, j)) + 1;
+  return n;
+}
+
+// The digit-ready form of a complemented z image (pre-pass 2 writes it under the digit loop):
+// digit j in byte j, so that the loop's index instructions, which read bits [7:0] of a scalar,
+// take digit 0 from the word itself and the others after one shift.  Every digit is masked to
+// its width here and to kClassDigitBits bits in class_digit_of: no index leaves its table.
+TW_BITS_HD uint32_t class_digit_encode(uint32_t zc, int nl) {
+  uint32_t w = 0;
+  for (int j = 0; j < kClassDigits; ++j)
+    w |= ((zc >> class_digit_shift(nl, j)) & ((1u << class_digit_width(nl, j)) - 1u)) << (8 * j);
+  return w;
+}
+TW_BITS_HD uint32_t class_digit_of(uint32_t word, int j) {
+  return (word >> (8 * j)) & ((1u << kClassDigitBits) - 1u);
+}
+
+// G_d of one digit of W planes for d = 0 .. 2^W, with the planes ANDed with E and entry 2^W = E
+// (lower digits: E = ~0; the top digit: the equal-top mask).  Built level by level: bit b of d
+// is z's mask of plane b, so an entry of b + 1 planes is the entry of its low b bits ANDed
+// (mask 0) or ORed (mask ones) with plane b — majority with a constant.  With old[0] = 0 and
+// old[2^b] = E both rules give plane b at d = 2^b.
+template <int W>
+TW_BITS_HD void class_digit_table(const uint32_t (&plane)[W], uint32_t E,
+                                  uint32_t (&G)[(1 << W) + 1]) {
+  G[0] = 0u, G[1] = plane[0] & E, G[2] = E;
+#pragma unroll
+  for (int b = 1; b < W; ++b) {
+    const uint32_t pb = plane[b] & E;
+    G[2 << b] = E;
+#pragma unroll
+    for (int d = (1 << b) - 1; d >= 1; --d) {
+      G[d + (1 << b)] = pb | G[d];
+      G[d] = pb & G[d];
+    }
+    G[1 << b] = pb;
+  }
+}
+
+// The tables of one x group: entry d of digit j at g[j][d], d = 0 .. 2^w; entries past that are
+// 0 and never read
+struct ClassDigitTables {
+  uint32_t g[kClassDigits][kClassDigitEntries];
+};
+template <int NL, int J>
+TW_BITS_HD void class_digit_tables_one(const uint32_t (&low)[NL], uint32_t E,
+                                       ClassDigitTables& t) {
+  constexpr int W = class_digit_width(NL, J), S = class_digit_shift(NL, J);
+  uint32_t pl[W], G[(1 << W) + 1];
+#pragma unroll
+  for (int b = 0; b < W; ++b) pl[b] = low[S + b];
+  class_digit_table<W>(pl, J == kClassDigits - 1 ? E : ~0u, G);
+#pragma unroll
+  for (int d = 0; d < kClassDigitEntries; ++d)
+    t.g[J][d] = d <= (1 << W) ? G[d <= (1 << W) ? d : 0] : 0u;
+}
+// low: the group's UNMASKED low planes; E: class_equal_mask of its G and P
+template <int NL>
+TW_BITS_HD void class_digit_tables(const uint32_t (&low)[NL], uint32_t E, ClassDigitTables& t) {
+  static_assert(class_digits_fit(NL), "low field too wide for the digit tables");
+  class_digit_tables_one<NL, 0>(low, E, t);
+  class_digit_tables_one<NL, 1>(low, E, t);
+  class_digit_tables_one<NL, 2>(low, E, t);
+  class_digit_tables_one<NL, 3>(low, E, t);
+}
+
+// class_gt32_masked by table lookup: word is a z image's digit-ready form (class_digit_encode)
+TW_BITS_HD ClassMasked class_gt32_digits(const ClassDigitTables& t, uint32_t G, uint32_t word) {
+  uint32_t c = t.g[0][class_digit_of(word, 0)];
+  for (int j = 1; j < kClassDigits; ++j) {
+    const uint32_t d = class_digit_of(word, j);
+    c = bits_carry(t.g[j][d], t.g[j][d + 1], c);
+  }
+  return ClassMasked{G, c};
+}
+
 // ---------------------------------------------------------------------------- the run table
 // Per bag: for each non-empty class, ceil(n_c / chunk) runs of near-equal length over the
 // class's range of the class-ordered region, classes in ascending order.  An entry is two u32
@@ -155,6 +265,8 @@ struct ClassPlan {
   int64_t chunk;      // longest run
   int64_t zs_stride;  // words per bag of the class-ordered region
   int64_t off_zs, off_cnt, off_tab;  // word offsets into the workspace
+  int digits;  // > 0: pre-pass 2 writes the images digit-ready for this many low planes (the
+               // launcher sets it for the digit loop; same words, same regions)
 };
 
 TW_BITS_HD ClassPlan class_plan(const PlanesPlan& p, int64_t max_nx, int64_t max_nz,
@@ -211,13 +323,21 @@ TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb,
 //   0  §4.1g's loop: bits_carry(G, P, c) per z, the images through a VGPR and v_readlane_b32
 //   1  masked low planes: the chain's carry is counted as it is, len * popc(G) once per item
 //   2  form 1 with the run read by scalar loads, TW_CLASS_BATCH images per load
+//   3  the digit tables (§4.1i) where the low field fits them (class_digits_fit(NB - K)):
+//      bits_count_class_digits; form 2 for every other (NB, K)
 #ifndef TW_CLASS_FORM
-#define TW_CLASS_FORM 2
+#define TW_CLASS_FORM 3
+#endif
+// the form bits_count_class itself runs in: under form 3 it is the fallback, form 2
+#if TW_CLASS_FORM == 3
+#define TW_CLASS_BASE 2
+#else
+#define TW_CLASS_BASE TW_CLASS_FORM
 #endif
 #ifndef TW_CLASS_BATCH
 #define TW_CLASS_BATCH 4
 #endif
-static_assert(TW_CLASS_FORM >= 0 && TW_CLASS_FORM <= 2, "TW_CLASS_FORM: 0, 1 or 2");
+static_assert(TW_CLASS_FORM >= 0 && TW_CLASS_FORM <= 3, "TW_CLASS_FORM: 0, 1, 2 or 3");
 static_assert(TW_CLASS_BATCH == 2 || TW_CLASS_BATCH == 4 || TW_CLASS_BATCH == 8 ||
                   TW_CLASS_BATCH == 16,
               "TW_CLASS_BATCH: a scalar load's width in words");
@@ -244,7 +364,7 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
                                                                int len, uint32_t cls, int lane) {
   constexpr int NL = NB - K;
   uint32_t lo[R][NL], acc[R];
-#if TW_CLASS_FORM == 0
+#if TW_CLASS_BASE == 0
   uint32_t G[R], P[R];
 #else
   uint32_t ng = 0;  // popc(G) over the groups: the class-constant term of one z
@@ -256,7 +376,7 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
     for (int b = 0; b < NL; ++b) lo[r][b] = pw[(r * NB + b) * 64 + lane];
 #pragma unroll
     for (int b = 0; b < K; ++b) top[b] = pw[(r * NB + NL + b) * 64 + lane];
-#if TW_CLASS_FORM == 0
+#if TW_CLASS_BASE == 0
     class_gp<K>(top, cls, G[r], P[r]);
 #else
     uint32_t g, p;
@@ -278,13 +398,13 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
       for (int r = 0; r < R; ++r) c[r] = bits_carry(lo[r][b], m[b], c[r]);
 #pragma unroll
     for (int r = 0; r < R; ++r)
-#if TW_CLASS_FORM == 0
+#if TW_CLASS_BASE == 0
       acc[r] = bits_popc_add(bits_carry(G[r], P[r], c[r]), acc[r]);
 #else
       acc[r] = bits_popc_add(c[r], acc[r]);
 #endif
   };
-#if TW_CLASS_FORM == 2
+#if TW_CLASS_BASE == 2
   constexpr int B = TW_CLASS_BATCH;
   typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
   const ConstWords zc = (ConstWords)(uintptr_t)zs;
@@ -325,11 +445,210 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
   unsigned long long tot = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) tot += acc[r];
-#if TW_CLASS_FORM != 0
+#if TW_CLASS_BASE != 0
   tot += (unsigned long long)(uint32_t)len * ng;  // the run's exact length
 #endif
   return tot;
 }
+// The loop form a launch of (nb, k) runs in this build
+constexpr int class_loop_form(int nb, int k) {
+  return TW_CLASS_FORM == 3 && !class_digits_fit(nb - k) ? 2 : TW_CLASS_FORM;
+}
+// Groups per item under the digit loop (build time: the register map of the largest sets the
+// kernel's VGPRs — 2: 4 waves per SIMD, 3: 3 waves, 4: 2 waves)
+#ifndef TW_CLASS_DIGIT_R
+#define TW_CLASS_DIGIT_R 2
+#endif
+static_assert(TW_CLASS_DIGIT_R >= 1 && TW_CLASS_DIGIT_R <= 4, "TW_CLASS_DIGIT_R: 1 .. 4");
+constexpr int kClassDigitsMaxR = TW_CLASS_DIGIT_R;
+
+#if TW_CLASS_FORM == 3
+// The digit loop.  A group's tables sit in FIXED VGPRs and the hardware's VGPR
+// index mode picks the entry: between s_set_gpr_idx_on and _off, M0[7:0] — a z digit — is added
+// to the register numbers of a VALU instruction's first two sources (mode 0x3), so
+//     v_mov_b32    c, v24                     c = G0[d0]
+//     v_bitop3_b32 c, v32, v33, c  0xE8       c = majority(G1[d1], G1[d1 + 1], c)
+// read v(24 + d0) and v(32 + d1), v(33 + d1); the third source and the destination are not
+// indexed.  Register map: v8 .. v23 the carries of a batch (image u, group g: v(8 + 4u + g));
+// group g's 36 table registers from v(24 + 36g): digit 0 at + 0 (8 entries), digits 1, 2, 3 at
+// + 8, + 17, + 26 (9 entries each), one spare.
+// Per z the scalar side shifts the digit-ready word (class_digit_encode) three times and sets
+// the index four times; per z and group the lane side issues 4 chain instructions and, after
+// _off — v_bcnt's operands would be indexed too — 1 popcount into the group's counter.  M0 and
+// MODE are written and consumed inside one asm statement (the compiler keeps nothing in M0
+// across a statement).  Only words pre-pass 2 encoded reach M0: every digit is below
+// 2^kClassDigitBits, so an indexed read stays inside its table.
+typedef uint32_t ClassVec4 __attribute__((ext_vector_type(4)));
+typedef uint32_t ClassVec32 __attribute__((ext_vector_type(32)));
+constexpr int kClassDigitGroupRegs = 36;
+static_assert(class_digit_table_regs(kClassDigitMaxNL) <= kClassDigitGroupRegs, "register map");
+// flat register of entry d of digit j inside a group's 36
+constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1) + d; }
+
+#define TW_DG_OP(C, A, B) "v_bitop3_b32 " C ", " A ", " B ", " C " bitop3:0xe8\n\t"
+#define TW_DG_MOV(C, A) "v_mov_b32 " C ", " A "\n\t"
+#define TW_DG_IDX(Z, T, SH) "s_lshr_b32 " T ", " Z ", " SH "\n\ts_set_gpr_idx_idx " T "\n\t"
+// digit steps of the groups: carry registers C0 .. C3 of one image
+#define TW_DG_D0_1(C0, C1, C2, C3) TW_DG_MOV(C0, "v24")
+#define TW_DG_D0_2(C0, C1, C2, C3) TW_DG_D0_1(C0, C1, C2, C3) TW_DG_MOV(C1, "v60")
+#define TW_DG_D0_3(C0, C1, C2, C3) TW_DG_D0_2(C0, C1, C2, C3) TW_DG_MOV(C2, "v96")
+#define TW_DG_D0_4(C0, C1, C2, C3) TW_DG_D0_3(C0, C1, C2, C3) TW_DG_MOV(C3, "v132")
+#define TW_DG_D1_1(C0, C1, C2, C3) TW_DG_OP(C0, "v32", "v33")
+#define TW_DG_D1_2(C0, C1, C2, C3) TW_DG_D1_1(C0, C1, C2, C3) TW_DG_OP(C1, "v68", "v69")
+#define TW_DG_D1_3(C0, C1, C2, C3) TW_DG_D1_2(C0, C1, C2, C3) TW_DG_OP(C2, "v104", "v105")
+#define TW_DG_D1_4(C0, C1, C2, C3) TW_DG_D1_3(C0, C1, C2, C3) TW_DG_OP(C3, "v140", "v141")
+#define TW_DG_D2_1(C0, C1, C2, C3) TW_DG_OP(C0, "v41", "v42")
+#define TW_DG_D2_2(C0, C1, C2, C3) TW_DG_D2_1(C0, C1, C2, C3) TW_DG_OP(C1, "v77", "v78")
+#define TW_DG_D2_3(C0, C1, C2, C3) TW_DG_D2_2(C0, C1, C2, C3) TW_DG_OP(C2, "v113", "v114")
+#define TW_DG_D2_4(C0, C1, C2, C3) TW_DG_D2_3(C0, C1, C2, C3) TW_DG_OP(C3, "v149", "v150")
+#define TW_DG_D3_1(C0, C1, C2, C3) TW_DG_OP(C0, "v50", "v51")
+#define TW_DG_D3_2(C0, C1, C2, C3) TW_DG_D3_1(C0, C1, C2, C3) TW_DG_OP(C1, "v86", "v87")
+#define TW_DG_D3_3(C0, C1, C2, C3) TW_DG_D3_2(C0, C1, C2, C3) TW_DG_OP(C2, "v122", "v123")
+#define TW_DG_D3_4(C0, C1, C2, C3) TW_DG_D3_3(C0, C1, C2, C3) TW_DG_OP(C3, "v158", "v159")
+// one image against R groups; the index already holds its digit 0
+#define TW_DG_Z(R, Z, T, C0, C1, C2, C3)                        \
+  TW_DG_D0_##R(C0, C1, C2, C3)                                  \
+  TW_DG_IDX(Z, T, "8") TW_DG_D1_##R(C0, C1, C2, C3)             \
+  TW_DG_IDX(Z, T, "16") TW_DG_D2_##R(C0, C1, C2, C3)            \
+  TW_DG_IDX(Z, T, "24") TW_DG_D3_##R(C0, C1, C2, C3)
+// the popcounts of one image's carries, after _off (their operands would be indexed too)
+#define TW_DG_CNT(C, A) "v_bcnt_u32_b32 " A ", " C ", " A "\n\t"
+#define TW_DG_C_1(C0, C1, C2, C3) TW_DG_CNT(C0, "%[a0]")
+#define TW_DG_C_2(C0, C1, C2, C3) TW_DG_C_1(C0, C1, C2, C3) TW_DG_CNT(C1, "%[a1]")
+#define TW_DG_C_3(C0, C1, C2, C3) TW_DG_C_2(C0, C1, C2, C3) TW_DG_CNT(C2, "%[a2]")
+#define TW_DG_C_4(C0, C1, C2, C3) TW_DG_C_3(C0, C1, C2, C3) TW_DG_CNT(C3, "%[a3]")
+#define TW_DG_ONE(R)                                            \
+  "s_set_gpr_idx_on %[z0], 0x3\n\t"                             \
+  TW_DG_Z(R, "%[z0]", "%[t]", "v8", "v9", "v10", "v11") "s_set_gpr_idx_off\n\t" \
+  TW_DG_C_##R("v8", "v9", "v10", "v11")
+// (the statement loads the next batch itself and waits for it after the chains: a load issued
+// outside would be waited for before the statement)
+#define TW_DG_BATCH(R)                                                                   \
+  "s_load_dwordx4 %[nx], %[p], 0x0\n\ts_set_gpr_idx_on %[z0], 0x3\n\t"                   \
+  TW_DG_Z(R, "%[z0]", "%[t]", "v8", "v9", "v10", "v11") "s_set_gpr_idx_idx %[z1]\n\t"   \
+  TW_DG_Z(R, "%[z1]", "%[t]", "v12", "v13", "v14", "v15") "s_set_gpr_idx_idx %[z2]\n\t" \
+  TW_DG_Z(R, "%[z2]", "%[t]", "v16", "v17", "v18", "v19") "s_set_gpr_idx_idx %[z3]\n\t" \
+  TW_DG_Z(R, "%[z3]", "%[t]", "v20", "v21", "v22", "v23") "s_set_gpr_idx_off\n\t"       \
+  TW_DG_C_##R("v8", "v9", "v10", "v11") TW_DG_C_##R("v12", "v13", "v14", "v15")         \
+  TW_DG_C_##R("v16", "v17", "v18", "v19") TW_DG_C_##R("v20", "v21", "v22", "v23")       \
+  "s_waitcnt lgkmcnt(0)"
+#define TW_DG_ACC_1(a) [a0] "+v"(a[0])
+#define TW_DG_ACC_2(a) TW_DG_ACC_1(a), [a1] "+v"(a[1])
+#define TW_DG_ACC_3(a) TW_DG_ACC_2(a), [a2] "+v"(a[2])
+#define TW_DG_ACC_4(a) TW_DG_ACC_3(a), [a3] "+v"(a[3])
+// (s_lshr_b32 writes SCC: without the clobber a compare is scheduled across the statement)
+#define TW_DG_CARRIES1 "scc", "v8", "v9", "v10", "v11"
+#define TW_DG_CARRIES4                                                                   \
+  TW_DG_CARRIES1, "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20", "v21", \
+      "v22", "v23"
+#define TW_DG_TAB_1(a, b) "{v[24:55]}"(a[0]), "{v[56:59]}"(b[0])
+#define TW_DG_TAB_2(a, b) TW_DG_TAB_1(a, b), "{v[60:91]}"(a[1]), "{v[92:95]}"(b[1])
+#define TW_DG_TAB_3(a, b) TW_DG_TAB_2(a, b), "{v[96:127]}"(a[2]), "{v[128:131]}"(b[2])
+#define TW_DG_TAB_4(a, b) TW_DG_TAB_3(a, b), "{v[132:163]}"(a[3]), "{v[164:167]}"(b[3])
+#define TW_DG_CASE_BATCH(R)                                                                \
+  if constexpr (kR == R)                                                                   \
+    asm volatile(TW_DG_BATCH(R)                                                            \
+                 : TW_DG_ACC_##R(acc), [t] "=&s"(t), [nx] "=&s"(next)                      \
+                 : [z0] "s"(z[0]), [z1] "s"(z[1]), [z2] "s"(z[2]), [z3] "s"(z[3]),         \
+                   [p] "s"(nz), TW_DG_TAB_##R(ta, tb)                                      \
+                 : TW_DG_CARRIES4);
+#define TW_DG_CASE_ONE(R)                                                                  \
+  if constexpr (kR == R)                                                                   \
+    asm volatile(TW_DG_ONE(R)                                                              \
+                 : TW_DG_ACC_##R(acc), [t] "=&s"(t)                                        \
+                 : [z0] "s"(z), TW_DG_TAB_##R(ta, tb)                                      \
+                 : TW_DG_CARRIES1);
+
+// bits_count_class under the digit loop: R <= kClassDigitsMaxR groups, the run's images at zs
+// digit-ready.  Whole batches of four images per asm statement, each loading the batch after it
+// (two statements per trip, the batches' registers swapping roles); the last len mod 4 images
+// one statement each from the batch already loaded, so exactly len images are evaluated and no
+// word past the run's end reaches M0.  A whole batch's load reads up to four words past the
+// run's end (never used): inside the workspace, as in form 2.
+constexpr int kClassDigitBatch = 4;  // images per statement and scalar load
+static_assert(kClassDigitBatch < 64, "the over-read must stay inside the count region");
+template <int NB, int K, int R>
+__device__ __forceinline__ unsigned long long bits_count_class_digits(
+    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zs, int len, uint32_t cls,
+    int lane) {
+  constexpr int NL = NB - K;
+  [[maybe_unused]] constexpr int kR = R;
+  static_assert(R >= 1 && R <= kClassDigitsMaxR, "the register map holds kClassDigitsMaxR groups");
+  ClassVec32 ta[R];
+  ClassVec4 tb[R];
+  uint32_t acc[R], ng = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    uint32_t low[NL], top[K], G, P;
+#pragma unroll
+    for (int b = 0; b < NL; ++b) low[b] = pw[(r * NB + b) * 64 + lane];
+#pragma unroll
+    for (int b = 0; b < K; ++b) top[b] = pw[(r * NB + NL + b) * 64 + lane];
+    class_gp<K>(top, cls, G, P);
+    ng = bits_popc_add(G, ng);
+    ClassDigitTables t;
+    class_digit_tables<NL>(low, class_equal_mask(G, P), t);
+    ta[r] = 0u, tb[r] = 0u;
+#pragma unroll
+    for (int j = 0; j < kClassDigits; ++j)
+#pragma unroll
+      for (int d = 0; d < (j == 0 ? 8 : kClassDigitEntries); ++d) {
+        const int f = class_digit_reg(j, d);
+        if (f < 32)
+          ta[r][f] = t.g[j][d];
+        else
+          tb[r][f - 32] = t.g[j][d];
+      }
+    acc[r] = 0;
+  }
+  typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+  // z: the four images to evaluate; the statement loads the four words at nz into next
+  auto batch = [&](const ClassVec4 z, ConstWords nz, ClassVec4& next) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t t;
+    TW_DG_CASE_BATCH(1) TW_DG_CASE_BATCH(2) TW_DG_CASE_BATCH(3) TW_DG_CASE_BATCH(4)
+#else
+    next = z;
+#endif
+  };
+  auto one = [&](uint32_t z) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t t;
+    TW_DG_CASE_ONE(1) TW_DG_CASE_ONE(2) TW_DG_CASE_ONE(3) TW_DG_CASE_ONE(4)
+#endif
+  };
+  ConstWords p = (ConstWords)(uintptr_t)zs;
+  ClassVec4 a, b;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) a[u] = p[u];
+  int j = 0;
+  for (; j + 8 <= len; j += 8, p += 8) {
+    batch(a, p + 4, b);
+    batch(b, p + 8, a);
+  }
+  if (j + 4 <= len) {
+    batch(a, p + 4, b);
+    a = b, j += 4;
+  }
+  for (; j < len; ++j) {  // a holds the images from j on: never a word past the run's end
+    one(a[0]);
+    a = a.yzww;
+  }
+  unsigned long long tot = (unsigned long long)(uint32_t)len * ng;  // the run's exact length
+#pragma unroll
+  for (int r = 0; r < R; ++r) tot += acc[r];
+  return tot;
+}
+// The instantiation for an item's ng <= R groups (wave-uniform): no group tests in the loop
+template <int NB, int K, int R>
+__device__ __forceinline__ unsigned long long bits_count_class_digits_of(
+    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zs, int len, uint32_t cls,
+    int lane, int ng) {
+  if constexpr (R > 1)
+    if (ng < R) return bits_count_class_digits_of<NB, K, R - 1>(pw, zs, len, cls, lane, ng);
+  return bits_count_class_digits<NB, K, R>(pw, zs, len, cls, lane);
+}
+#endif  // TW_CLASS_FORM == 3
 #endif  // __HIPCC__
 
 }  // namespace tw
