@@ -231,6 +231,13 @@ int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_
  * (DESIGN §4.1h, §4.1i): 3 = the digit tables, where nb - k low planes fit them; 2 = masked
  * planes and scalar loads; 0, 1 in A/B builds only.  A query: there is no hook to set it. */
 int32_t tw_count_chain_class_form(int32_t nb, int32_t k);
+/* A/B control of the digit loop's items: an item walks a span of `runs`
+ * consecutive run-table entries of its bag and keeps what depends on its x tile alone across
+ * them.  runs >= 1 forces the span (clamped to each launch's table capacity; 1 is one item per
+ * entry), 0 restores the automatic rule (chainclass.h class_span_auto), -1 only reports, any
+ * other value changes nothing.  Returns the setting in force before the call.  Process-global;
+ * same counts; the masked-plane loop (form 2) always runs one entry per item. */
+int32_t tw_count_chain_class_span(int32_t runs);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
  * estimation-experiment/main.py:29-31's integer): each bag's z images (integers in
  * [0, z_total], z_total = the Z count the images were ranked against) counting-sorted into

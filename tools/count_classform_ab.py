@@ -11,7 +11,13 @@ interleaved over 7 rounds; per setting the median, min and max ms of the whole n
 agree exactly.
 Run on the GPU box:  python tools/count_classform_ab.py [out.json [variant ...]]
 (variants by file suffix, e.g. classform1 classform2b16 classform3r2 — form 3, the digit
-tables, with R groups per item; default: every library present)"""
+tables, with R groups per item; default: every library present)
+
+--spans [out.json]: the span sweep of DESIGN §4.1j on the same shapes with the product library:
+under the automatic class bits and swap rule, tw_count_chain_class_span forced to 1, 2, 4, 8,
+16, 32 and the whole bag, and the automatic rule, interleaved over the rounds; per shape and
+span the median, min and max ms, the ratio of medians to M = 1 of the same process, and M = 1's
+own spread (max - min) / median, against which a shape's automatic setting is judged."""
 import json
 import os
 import pathlib
@@ -21,8 +27,12 @@ import sys
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 VARIANTS = ROOT / "tools" / "variants"
 ROUNDS, REPS = 7, 2
-SETTINGS = [("k=0", 0, 1), ("automatic", -1, 1), ("automatic, swap 0", -1, 0),
-            ("automatic, swap 2", -1, 2)]
+# (name, class bits, swap, span): span 0 is the automatic rule
+SETTINGS = [("k=0", 0, 1, 0), ("automatic", -1, 1, 0), ("automatic, swap 0", -1, 0, 0),
+            ("automatic, swap 2", -1, 2, 0)]
+WHOLE_BAG = 1 << 20  # (clamped to the launch's table capacity)
+SPAN_SETTINGS = [("M=1", -1, 1, 1)] + [(f"M={m}", -1, 1, m) for m in (2, 4, 8, 16, 32)] + [
+    ("M=whole bag", -1, 1, WHOLE_BAG), ("automatic", -1, 1, 0)]
 # (name, G, K): G ranks share the strong problem; G = 0: C2; G = -1: 64 bags per step of
 # 7 * 2048 + 100 x images, a remainder small enough that class_swap_mode keeps it swapped
 SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1, 4),
@@ -30,7 +40,7 @@ SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1
           ("G=8 K=20", 8, 20), ("C2", 0, 1), ("remainder 100 K=20", -1, 20)]
 
 
-def child():
+def child(settings=SETTINGS, base="k=0"):
     sys.path.insert(0, str(ROOT))
     import numpy as np
     import torch
@@ -56,7 +66,7 @@ def child():
         out = torch.empty((K, Nl), dtype=torch.int64, device="cuda")
         wb = int(L.lib().tw_chain_planes_work_bytes(Nl, K, k, kz, 0, bound))
         work = torch.empty(max(wb, 256), dtype=torch.uint8, device="cuda")
-        ts = {s[0]: [] for s in SETTINGS}
+        ts = {s[0]: [] for s in settings}
         ref = None
 
         def call():
@@ -64,9 +74,10 @@ def child():
                    out, L.stream_handle(), work, wb)
         try:
             for _ in range(ROUNDS):
-                for sname, bits, swap in SETTINGS:
+                for sname, bits, swap, span in settings:
                     L.call("tw_count_chain_set_class_bits", bits)
                     L.call("tw_count_chain_set_swap", swap)
+                    L.lib().tw_count_chain_class_span(span)
                     e0 = torch.cuda.Event(enable_timing=True)
                     e1 = torch.cuda.Event(enable_timing=True)
                     call()  # warm
@@ -81,11 +92,38 @@ def child():
         finally:
             L.call("tw_count_chain_set_class_bits", -1)
             L.call("tw_count_chain_set_swap", 1)
+            L.lib().tw_count_chain_class_span(0)
         ms = {s: {"median": float(np.median(t)), "min": float(min(t)), "max": float(max(t))}
               for s, t in ts.items()}
         report.append({"shape": name, "bags": K * Nl, "nx": k, "nz": kz, "ms": ms,
-                       "ratio to k=0": {s: ms[s]["median"] / ms["k=0"]["median"] for s in ms}})
+                       f"ratio to {base}": {s: ms[s]["median"] / ms[base]["median"] for s in ms},
+                       f"spread of {base}": (ms[base]["max"] - ms[base]["min"]) / ms[base]["median"]})
     print(json.dumps(report))
+
+
+def spans_main():
+    """One child per pass, the product library: the span sweep."""
+    out = sys.argv[2] if len(sys.argv) > 2 else None
+    env = dict(os.environ)
+    env.pop("TW_LIB_PATH", None)
+    passes = []
+    for rep in range(REPS):
+        r = subprocess.run([sys.executable, __file__, "--spans-child"], env=env,
+                           capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            print("failed:", r.stderr[-1500:], flush=True)
+            sys.exit(1)
+        rows = json.loads(r.stdout.strip().splitlines()[-1])
+        passes.append(rows)
+        for row in rows:
+            print(f"pass {rep} {row['shape']}: spread of M=1 {row['spread of M=1']:.4f}  " + "  ".join(
+                f"{s[0]} {row['ratio to M=1'][s[0]]:.4f}" for s in SPAN_SETTINGS[1:]), flush=True)
+        if out:
+            pathlib.Path(out).write_text(json.dumps(
+                {"what": "tw_count_pairs_chain_planes under forced spans (tw_count_chain_class_span)"
+                         " and the automatic rule: ms of the whole native call and the ratio of "
+                         "medians to M = 1 inside each child; one child per pass",
+                 "passes": passes}, indent=1) + "\n")
 
 
 def main():
@@ -120,4 +158,11 @@ def main():
 
 
 if __name__ == "__main__":
-    child() if sys.argv[1:2] == ["--child"] else main()
+    if sys.argv[1:2] == ["--child"]:
+        child()
+    elif sys.argv[1:2] == ["--spans-child"]:
+        child(SPAN_SETTINGS, "M=1")
+    elif sys.argv[1:2] == ["--spans"]:
+        spans_main()
+    else:
+        main()

@@ -251,6 +251,7 @@ _SIGNATURES = {
     "tw_self_sorted_chunk": [],
     "tw_self_sorted": [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
     "tw_count_chain_class_form": [_i32, _i32],
+    "tw_count_chain_class_span": [_i32],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,

@@ -721,15 +721,18 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
   }
 }
 
-// The count on class runs: per bag p.tiles_x x cp.cap class items (tile-major: a block's waves
-// read the same planes).  An item whose entry is past the bag's count exits at once; an active
-// one reads its run {z0, len, class} and counts its up to p.R x groups against exactly those
-// len images.  The plan's swapped items run in a launch of their own (k_count_chain_swapped):
+// The count on class runs: per bag p.tiles_x x class_spans(cp.cap, cp.span) class items
+// (tile-major: a block's waves read the same planes), an item the cp.span consecutive table
+// entries of one span (chainclass.h).  An item whose span starts past the bag's
+// count exits at once; an active one reads its runs {z0, len, class} and counts its up to p.R
+// x groups against exactly those len images each.  Under the digit loop an item keeps what
+// depends on its x tile alone across the span; the masked-plane loop runs at cp.span = 1.
+// The plan's swapped items run in a launch of their own (k_count_chain_swapped):
 // their full-NB loop holds R * NB planes per lane, and without it this kernel allocates 89
 // VGPRs at NB = 20, k = 8 (at most 94 at NB <= 20) — 5 waves per SIMD instead of 4 at the 105
 // of the joint kernel.  Where the low field fits the digit tables (form 3, DESIGN
-// §4.1i) the run's images are digit-ready and the item runs bits_count_class_digits: about
-// 100 VGPRs, 4 waves.
+// §4.1i, §4.1j) the runs' images are digit-ready and the item runs bits_count_span_digits: 122
+// VGPRs at NL = 12 (4 waves), 96 at narrower low fields (5 waves), as before the spans.
 template <int NB, int K>
 __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
     const int64_t* __restrict__ x_off, const int64_t* __restrict__ z_off, int n_shards,
@@ -739,44 +742,51 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int lane = threadIdx.x & (kWave - 1);
   const int item = lb * (kBlock / kWave) + wid;
-  const int n_class = p.tiles_x * cp.cap;
+  const int spans = class_spans(cp.cap, cp.span);
+  const int n_class = p.tiles_x * spans;
   const int v = item / n_class;
   bool active = v < n_bags;
   unsigned long long tot = 0;
   if (active) {
     const int s = v % n_shards;
     const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
-    const int rem = item - v * n_class;
-    const int tx = rem / cp.cap, e = rem - tx * cp.cap;
+    const ClassSpanItem si = class_span_item(item - v * n_class, spans);
     const PlanesBag bag = planes_bag(nx, nz, p.swap != 0);
     const int lim = bag.xgroups < p.gx ? bag.xgroups : p.gx;
-    const int g0 = tx * p.R;
+    const int g0 = si.tx * p.R;
     const int ng = __builtin_amdgcn_readfirstlane(lim - g0 < p.R ? lim - g0 : p.R);
-    active = ng > 0 && e < (int)work[cp.off_cnt + v];
+    // (the bag's count is <= cp.cap: no entry past the bag's table is read)
+    const ClassSpan sp = class_span_entries(
+        si.q, cp.span, __builtin_amdgcn_readfirstlane((int)work[cp.off_cnt + v]));
+    active = ng > 0 && sp.e0 < sp.e1;
     if (active) {
-      const uint32_t* __restrict__ tab = work + (cp.off_tab + ((int64_t)v * cp.cap + e) * 2);
-      const ClassRun r = class_entry((uint32_t)__builtin_amdgcn_readfirstlane((int)tab[0]),
-                                     (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[1]));
+      const uint32_t* __restrict__ tab =
+          work + bits_uniform(cp.off_tab + ((int64_t)v * cp.cap + sp.e0) * 2);
       const uint32_t* __restrict__ pw =
           work + bits_uniform(planes_word(NB, (int64_t)v * p.gx + g0, 0, 0));
-      const uint32_t* __restrict__ zs =
-          work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride + r.z0);
-      const int len = (int)r.len;  // >= 1: only non-empty classes have runs
+      const uint32_t* __restrict__ zbag =
+          work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride);
       unsigned long long t;
 #if TW_CLASS_FORM == 3
       if constexpr (class_loop_form(NB, K) == 3) {  // the digit loop: the launcher planned
-        t = bits_count_class_digits_of<NB, K, kClassDigitsMaxR>(  // R <= kClassDigitsMaxR
-            pw, zs, len, r.cls, lane, ng);
+        t = bits_count_span_digits_of<NB, K, kClassDigitsMaxR>(  // R <= kClassDigitsMaxR
+            pw, zbag, tab, sp.e1 - sp.e0, lane, ng);
       } else
 #endif
-      if (ng == 4)
-        t = bits_count_class<NB, K, 4>(pw, zs, len, r.cls, lane);
-      else if (ng == 3)
-        t = bits_count_class<NB, K, 3>(pw, zs, len, r.cls, lane);
-      else if (ng == 2)
-        t = bits_count_class<NB, K, 2>(pw, zs, len, r.cls, lane);
-      else
-        t = bits_count_class<NB, K, 1>(pw, zs, len, r.cls, lane);
+      {  // the masked-plane loop: one run per item (the launcher planned cp.span = 1)
+        const ClassRun r = class_entry((uint32_t)__builtin_amdgcn_readfirstlane((int)tab[0]),
+                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[1]));
+        const uint32_t* __restrict__ zs = zbag + r.z0;
+        const int len = (int)r.len;  // >= 1: only non-empty classes have runs
+        if (ng == 4)
+          t = bits_count_class<NB, K, 4>(pw, zs, len, r.cls, lane);
+        else if (ng == 3)
+          t = bits_count_class<NB, K, 3>(pw, zs, len, r.cls, lane);
+        else if (ng == 2)
+          t = bits_count_class<NB, K, 2>(pw, zs, len, r.cls, lane);
+        else
+          t = bits_count_class<NB, K, 1>(pw, zs, len, r.cls, lane);
+      }
       tot = wave_sum_u64(t);
     }
   }
@@ -968,6 +978,7 @@ static int g_chain_R = 0;  // tuning hooks (tw_count_chain_set_plan); 0 = automa
 static int64_t g_chain_zchunk = 0;
 static int g_planes_swap = 1;  // (tw_count_chain_set_swap: 0 never, 1 automatic, 2 always)
 static int g_class_bits = -1;  // (tw_count_chain_set_class_bits: -1 automatic, 0 off, 1..8)
+static int g_class_span = 0;   // (tw_count_chain_class_span: 0 automatic, >= 1 entries per item)
 
 // strict: R in {16, 8} x-images per lane, least padded slots (ties to 16); half: R = 8 {g, h}
 // pairs (the same 8 packed registers per lane).  z chunks: as many as give ~150 work items per
@@ -1519,7 +1530,8 @@ static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, 
                          dim3((unsigned)ceil_div((int64_t)bags * n_swapped, kBlock / kWave)),
                          dim3(kBlock), 0, st, xb, d_x_off, x_stride, d_z_off, n_shards, bags, p,
                          (const uint32_t*)work, o);
-    const dim3 g((unsigned)ceil_div((int64_t)bags * p.tiles_x * cp.cap, kBlock / kWave)),
+    const dim3 g((unsigned)ceil_div(
+                     (int64_t)bags * p.tiles_x * class_spans(cp.cap, cp.span), kBlock / kWave)),
         b(kBlock);
 #define TW_CLASS_CASE(K)                                                                       \
   case K:                                                                                      \
@@ -1572,9 +1584,19 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   const bool digits = k > 0 && class_loop_form(nb, k) == 3;
   int R = g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0;
   if (digits) R = R == 0 || R > kClassDigitsMaxR ? kClassDigitsMaxR : R;
-  const PlanesPlan p = planes_plan(max_nx, max_nz, bags, R, g_chain_zchunk,
-                                   class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k));
-  ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k);
+  // (a padded slot's price in the swap rule is that of the loop this launch runs)
+  const PlanesPlan p =
+      planes_plan(max_nx, max_nz, bags, R, g_chain_zchunk,
+                  class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k,
+                                  digits ? kClassDigits + 1 : 0));
+  // entries per item: the digit loop walks a span (forced, or chainclass.h's automatic rule);
+  // the masked-plane loop's registers are class-dependent throughout: one run per item
+  int64_t runs = 1;
+  if (digits)
+    runs = g_class_span > 0
+               ? g_class_span
+               : class_span_auto(bags, p.tiles_x, (int)class_capacity(max_nz, k, p.z_chunk));
+  ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k, runs);
   cp.digits = digits ? nb - k : 0;
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
                    bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&
@@ -1608,6 +1630,15 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
 // (chainclass.h TW_CLASS_FORM; 3: the digit tables, where the low field fits them)
 extern "C" int32_t tw_count_chain_class_form(int32_t nb, int32_t k) {
   return class_loop_form(nb, k);
+}
+
+// The table entries an item of the digit loop walks (chainclass.h): runs >= 1
+// forces that many (clamped to each launch's capacity), 0 restores the automatic rule, -1 only
+// reports; any other value changes nothing.  Returns the setting in force before the call.
+extern "C" int32_t tw_count_chain_class_span(int32_t runs) {
+  const int32_t before = g_class_span;
+  if (runs >= 0) g_class_span = runs;
+  return before;
 }
 
 extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,

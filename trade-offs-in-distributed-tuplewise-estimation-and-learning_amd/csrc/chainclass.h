@@ -258,24 +258,74 @@ TW_BITS_HD int64_t class_work_words(int64_t max_nz, int64_t n_bags) {
          class_round64(n_bags);
 }
 
+// ------------------------------------------------------------------------------- the spans
+// An item of the class count walks a SPAN of M consecutive table entries of its bag on one x
+// tile: what it builds from the tile alone — the low digit tables — serves all
+// of them.  Span q of a bag holds entries [q M, min((q + 1) M, cnt)), cnt the bag's entry count;
+// the launch reserves class_spans(cap, M) spans per bag and tile, tile-major, and a span past
+// the bag's count exits.  M = 1 is the launch of one item per entry.
+TW_BITS_HD int class_span_clamp(int64_t runs, int cap) {
+  return (int)(runs < 1 ? 1 : runs > cap ? (cap < 1 ? 1 : cap) : runs);
+}
+TW_BITS_HD int class_spans(int cap, int m) { return (cap + m - 1) / m; }
+struct ClassSpan {
+  int e0, e1;  // the entries [e0, e1) of span q; empty: e0 >= e1
+};
+TW_BITS_HD ClassSpan class_span_entries(int q, int m, int cnt) {
+  const int64_t a = (int64_t)q * m, b = a + m;
+  return ClassSpan{(int)(a < cnt ? a : cnt), (int)(b < cnt ? b : cnt)};
+}
+struct ClassSpanItem {
+  int tx, q;  // x tile and span of slot rem in [0, tiles_x * spans)
+};
+TW_BITS_HD ClassSpanItem class_span_item(int rem, int spans) {
+  const int tx = rem / spans;
+  return ClassSpanItem{tx, rem - tx * spans};
+}
+
+// The automatic span: the largest power of two M <= kClassSpanMax that still leaves the launch
+// kClassSpanFill items for every wave the chip holds at the digit loop's four waves per SIMD
+// (256 CUs x 4 SIMDs x 4 waves); with few bags long spans leave CUs idle (32 bags: M = 32 took
+// 1.49x the time of M = 1, M = 8 0.89x).  Past 8 the setup left to spread is about 1 % of an
+// item's instructions and the sweep no longer orders the spans: 16 was the faster at 20-step
+// launches of 64 bags per step (0.76 against 0.78 of M = 1) and the slower at 32-step ones (0.79
+// against 0.75).  Sweep: profiles/r13_classspan_ab.json.
+constexpr int kClassSpanMax = 8;
+constexpr int64_t kClassSpanFill = 1, kClassSpanChipWaves = 256 * 4 * 4;
+TW_BITS_HD int class_span_auto(int64_t n_bags, int tiles_x, int cap) {
+  int m = 1;
+  while (2 * m <= kClassSpanMax && 2 * m <= cap &&
+         n_bags * tiles_x * class_spans(cap, 2 * m) >= kClassSpanFill * kClassSpanChipWaves)
+    m *= 2;
+  return m;
+}
+
 struct ClassPlan {
   int k;              // class bits; 0: classes off (k_count_chain_planes)
   int cap;            // table entries per bag of this launch
-  int per_bag;        // items per bag: tiles_x * cap + tiles_s * schunks
+  int per_bag;        // items per bag: tiles_x * class_spans(cap, span) + tiles_s * schunks
   int64_t chunk;      // longest run
   int64_t zs_stride;  // words per bag of the class-ordered region
   int64_t off_zs, off_cnt, off_tab;  // word offsets into the workspace
   int digits;  // > 0: pre-pass 2 writes the images digit-ready for this many low planes (the
                // launcher sets it for the digit loop; same words, same regions)
+  int span;    // table entries an item walks (1 .. cap; the masked-plane loop: always 1)
 };
 
+// A lane's u32 sums over a span — its popcounts, at most 32 per image and group, and
+// len * popc(G) — stay below 2^32 for every span inside one bag: bags hold fewer than 2^24 z
+// (checked where the workspace is taken) and an item has at most four groups.
+constexpr int64_t kClassMaxBagZ = (int64_t)1 << 24;
+static_assert(kClassMaxBagZ * 32 * 4 * 2 <= ((int64_t)1 << 32), "a span's u32 lane sums");
+
 TW_BITS_HD ClassPlan class_plan(const PlanesPlan& p, int64_t max_nx, int64_t max_nz,
-                                int64_t n_bags, int nb, int k) {
+                                int64_t n_bags, int nb, int k, int64_t runs = 1) {
   ClassPlan c{};
   c.k = k;
   c.chunk = class_chunk(p.z_chunk);
   c.cap = (int)class_capacity(max_nz, k, p.z_chunk);
-  c.per_bag = p.tiles_x * c.cap + p.tiles_s * p.schunks;
+  c.span = class_span_clamp(runs, c.cap);
+  c.per_bag = p.tiles_x * class_spans(c.cap, c.span) + p.tiles_s * p.schunks;
   c.zs_stride = class_round64(max_nz);
   c.off_zs = planes_work_words(max_nx, max_nz, n_bags, nb);
   c.off_cnt = c.off_zs + n_bags * c.zs_stride;
@@ -312,10 +362,14 @@ TW_BITS_HD int class_bits_auto(int64_t max_nz, int64_t n_bags, int nb) {
 // shape (rx = 1289, nz = 15625, NB = 20, k = 8: 219 k against 203 k) that is no swap, measured
 // 0.93-0.95 of the swapped launch's time; a remainder of a few images stays
 // swapped.  Forced settings and launches without classes are left alone.
-TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb, int k) {
+// slot_valu: what a padded slot costs per z and group in the loop the launch runs — 0 stands
+// for the masked-plane loop's NL + 1; the digit loop passes kClassDigits + 1.
+TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb, int k,
+                               int slot_valu = 0) {
   if (k == 0 || swap != 1) return swap;
   const int64_t rx = max_nx % kPlaneGroup, zg = planes_ceil_div(max_nz, kPlaneGroup);
-  return rx * zg * (4 * nb + 5) < max_nz * 4 * (nb - k + 1) ? 1 : 0;
+  const int64_t slot = slot_valu > 0 ? slot_valu : nb - k + 1;
+  return rx * zg * (4 * nb + 5) < max_nz * 4 * slot ? 1 : 0;
 }
 
 #if defined(__HIPCC__)
@@ -324,7 +378,7 @@ TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb,
 //   1  masked low planes: the chain's carry is counted as it is, len * popc(G) once per item
 //   2  form 1 with the run read by scalar loads, TW_CLASS_BATCH images per load
 //   3  the digit tables (§4.1i) where the low field fits them (class_digits_fit(NB - K)):
-//      bits_count_class_digits; form 2 for every other (NB, K)
+//      bits_count_span_digits; form 2 for every other (NB, K)
 #ifndef TW_CLASS_FORM
 #define TW_CLASS_FORM 3
 #endif
@@ -559,49 +613,72 @@ constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1
                  : [z0] "s"(z), TW_DG_TAB_##R(ta, tb)                                      \
                  : TW_DG_CARRIES1);
 
-// bits_count_class under the digit loop: R <= kClassDigitsMaxR groups, the run's images at zs
-// digit-ready.  Whole batches of four images per asm statement, each loading the batch after it
+// The class count of one item under the digit loop: R <= kClassDigitsMaxR groups
+// against the n >= 1 runs of a SPAN, whose table entries start at tab; the bag's class-ordered
+// images, digit-ready, at zbag.  Once per item: the groups' planes are loaded, digit tables 0-2
+// — which depend on the x tile alone — go to their pinned registers, and the K top planes and
+// the top digit's planes stay in registers or are reloaded per class (kKeep below: whichever
+// keeps the instantiation's waves per SIMD).  Per run of a new class: G, P and E, popc(G), and
+// the top digit's entries (flat registers 26 .. 34 of the group: they span the ClassVec32 /
+// ClassVec4 pair); consecutive runs of one class — a class longer than the chunk — keep them.
+//  Per run: whole batches of four images per asm statement, each loading the batch after it
 // (two statements per trip, the batches' registers swapping roles); the last len mod 4 images
 // one statement each from the batch already loaded, so exactly len images are evaluated and no
 // word past the run's end reaches M0.  A whole batch's load reads up to four words past the
 // run's end (never used): inside the workspace, as in form 2.
+//  The lane sums are u32 over the whole span: see kClassMaxBagZ.
 constexpr int kClassDigitBatch = 4;  // images per statement and scalar load
 static_assert(kClassDigitBatch < 64, "the over-read must stay inside the count region");
 template <int NB, int K, int R>
-__device__ __forceinline__ unsigned long long bits_count_class_digits(
-    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zs, int len, uint32_t cls,
-    int lane) {
+__device__ __forceinline__ unsigned long long bits_count_span_digits(
+    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zbag,
+    const uint32_t* __restrict__ tab, int n, int lane) {
   constexpr int NL = NB - K;
+  constexpr int kTop = kClassDigits - 1;  // the digit whose planes are ANDed with E
+  constexpr int W3 = class_digit_width(NL, kTop), S3 = class_digit_shift(NL, kTop);
   [[maybe_unused]] constexpr int kR = R;
   static_assert(R >= 1 && R <= kClassDigitsMaxR, "the register map holds kClassDigitsMaxR groups");
+  // The class-dependent planes (K top, W3 of the top digit) stay in registers where the tables
+  // fill the register map anyway (NL = 12: 4 waves per SIMD with or without them); at narrower
+  // low fields the map ends at v95 — 5 waves — and a new class reloads them (cache hits).
+  constexpr bool kKeep = NL == kClassDigitMaxNL;
+  constexpr int RK = kKeep ? R : 1;
   ClassVec32 ta[R];
   ClassVec4 tb[R];
-  uint32_t acc[R], ng = 0;
+  [[maybe_unused]] uint32_t top[RK][K], hi[RK][W3];
+  uint32_t acc[R];
+  auto place = [&](int r, int j, int d, uint32_t v) {
+    const int f = class_digit_reg(j, d);
+    if (f < 32)
+      ta[r][f] = v;
+    else
+      tb[r][f - 32] = v;
+  };
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    uint32_t low[NL], top[K], G, P;
+    uint32_t low[NL];
 #pragma unroll
     for (int b = 0; b < NL; ++b) low[b] = pw[(r * NB + b) * 64 + lane];
+    if constexpr (kKeep) {
 #pragma unroll
-    for (int b = 0; b < K; ++b) top[b] = pw[(r * NB + NL + b) * 64 + lane];
-    class_gp<K>(top, cls, G, P);
-    ng = bits_popc_add(G, ng);
+      for (int b = 0; b < K; ++b) top[r][b] = pw[(r * NB + NL + b) * 64 + lane];
+#pragma unroll
+      for (int b = 0; b < W3; ++b) hi[r][b] = low[S3 + b];
+    }
     ClassDigitTables t;
-    class_digit_tables<NL>(low, class_equal_mask(G, P), t);
+    class_digit_tables_one<NL, 0>(low, ~0u, t);
+    class_digit_tables_one<NL, 1>(low, ~0u, t);
+    class_digit_tables_one<NL, 2>(low, ~0u, t);
     ta[r] = 0u, tb[r] = 0u;
 #pragma unroll
-    for (int j = 0; j < kClassDigits; ++j)
+    for (int j = 0; j < kTop; ++j)
 #pragma unroll
-      for (int d = 0; d < (j == 0 ? 8 : kClassDigitEntries); ++d) {
-        const int f = class_digit_reg(j, d);
-        if (f < 32)
-          ta[r][f] = t.g[j][d];
-        else
-          tb[r][f - 32] = t.g[j][d];
-      }
+      for (int d = 0; d < (j == 0 ? 8 : kClassDigitEntries); ++d) place(r, j, d, t.g[j][d]);
     acc[r] = 0;
   }
   typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+  const ConstWords ct = (ConstWords)(uintptr_t)tab;
+  const ConstWords zc = (ConstWords)(uintptr_t)zbag;
   // z: the four images to evaluate; the statement loads the four words at nz into next
   auto batch = [&](const ClassVec4 z, ConstWords nz, ClassVec4& next) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -617,36 +694,66 @@ __device__ __forceinline__ unsigned long long bits_count_class_digits(
     TW_DG_CASE_ONE(1) TW_DG_CASE_ONE(2) TW_DG_CASE_ONE(3) TW_DG_CASE_ONE(4)
 #endif
   };
-  ConstWords p = (ConstWords)(uintptr_t)zs;
-  ClassVec4 a, b;
+  uint32_t ng = 0, cg = 0;  // popc(G) over the groups of the class at hand; sum of len * ng
+  uint32_t cls = ~0u;       // (no class)
+  for (int e = 0; e < n; ++e) {
+    const ClassRun run = class_entry(ct[2 * e], ct[2 * e + 1]);
+    if (run.cls != cls) {  // wave-uniform
+      cls = run.cls;
+      ng = 0;
+      int ql = lane;  // (opaque per class: the reloads are not hoisted out of the span)
+#if defined(__HIP_DEVICE_COMPILE__)
+      if constexpr (!kKeep) asm volatile("" : "+v"(ql));
+#endif
 #pragma unroll
-  for (int u = 0; u < 4; ++u) a[u] = p[u];
-  int j = 0;
-  for (; j + 8 <= len; j += 8, p += 8) {
-    batch(a, p + 4, b);
-    batch(b, p + 8, a);
+      for (int r = 0; r < R; ++r) {
+        uint32_t G, P, g[(1 << W3) + 1], tp[K], hp[W3];
+#pragma unroll
+        for (int b = 0; b < K; ++b)
+          tp[b] = kKeep ? top[kKeep ? r : 0][b] : pw[(r * NB + NL + b) * 64 + ql];
+#pragma unroll
+        for (int b = 0; b < W3; ++b)
+          hp[b] = kKeep ? hi[kKeep ? r : 0][b] : pw[(r * NB + S3 + b) * 64 + ql];
+        class_gp<K>(tp, cls, G, P);
+        ng = bits_popc_add(G, ng);
+        class_digit_table<W3>(hp, class_equal_mask(G, P), g);
+#pragma unroll
+        for (int d = 1; d <= (1 << W3); ++d) place(r, kTop, d, g[d]);  // (entry 0 stays 0)
+      }
+    }
+    const int len = (int)run.len;  // >= 1: only non-empty classes have runs
+    cg += (uint32_t)len * ng;      // the run's exact length
+    ConstWords p = zc + run.z0;
+    ClassVec4 a, b;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = p[u];
+    int j = 0;
+    for (; j + 8 <= len; j += 8, p += 8) {
+      batch(a, p + 4, b);
+      batch(b, p + 8, a);
+    }
+    if (j + 4 <= len) {
+      batch(a, p + 4, b);
+      a = b, j += 4;
+    }
+    for (; j < len; ++j) {  // a holds the images from j on: never a word past the run's end
+      one(a[0]);
+      a = a.yzww;
+    }
   }
-  if (j + 4 <= len) {
-    batch(a, p + 4, b);
-    a = b, j += 4;
-  }
-  for (; j < len; ++j) {  // a holds the images from j on: never a word past the run's end
-    one(a[0]);
-    a = a.yzww;
-  }
-  unsigned long long tot = (unsigned long long)(uint32_t)len * ng;  // the run's exact length
+  unsigned long long tot = cg;
 #pragma unroll
   for (int r = 0; r < R; ++r) tot += acc[r];
   return tot;
 }
 // The instantiation for an item's ng <= R groups (wave-uniform): no group tests in the loop
 template <int NB, int K, int R>
-__device__ __forceinline__ unsigned long long bits_count_class_digits_of(
-    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zs, int len, uint32_t cls,
-    int lane, int ng) {
+__device__ __forceinline__ unsigned long long bits_count_span_digits_of(
+    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zbag,
+    const uint32_t* __restrict__ tab, int n, int lane, int ng) {
   if constexpr (R > 1)
-    if (ng < R) return bits_count_class_digits_of<NB, K, R - 1>(pw, zs, len, cls, lane, ng);
-  return bits_count_class_digits<NB, K, R>(pw, zs, len, cls, lane);
+    if (ng < R) return bits_count_span_digits_of<NB, K, R - 1>(pw, zbag, tab, n, lane, ng);
+  return bits_count_span_digits<NB, K, R>(pw, zbag, tab, n, lane);
 }
 #endif  // TW_CLASS_FORM == 3
 #endif  // __HIPCC__
