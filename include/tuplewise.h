@@ -1188,6 +1188,49 @@ int tw_self_sorted(const void* d_s, const int64_t* d_off, int32_t n_shards, int6
                    int64_t max_n, int32_t dtype, int32_t kern, int32_t chunk, void* d_work,
                    void* d_out, void* stream);
 
+/* ---- Two-sample triplet U-statistics of degree (2,1) (csrc/triplets.hip; tuplewise.triplets;
+ * DESIGN.md §4.10; an extension, not in the reference): h = 1{D(x_i, z_k) > D(x_i, x_j)}, j != i,
+ * for an anchor x_i, a point x_j of its own class and a point z_k of the other class.  d_x is
+ * (rows, d) and d_z (rows, d) float64, row-major, 1 <= d <= 64.  D(a, b) is the squared
+ * Euclidean distance in ONE arithmetic order, multiply and add separate (never fused):
+ *   acc = 0.0; for c = 0 .. d-1: t = a_c - b_c; acc = acc + t * t
+ * so a distance has the same bits wherever it is computed; a NaN distance is
+ * written as the quiet NaN 0x7ff8000000000000, whichever NaN the arithmetic returned.
+ *
+ * tw_triplet_rows writes, for every anchor a in [a_begin, a_end) (absolute rows of d_x), the two
+ * rows whose two-sample count is the anchor's triplet count.  The partition is given by block
+ * offsets: block b owns rows [d_blk_x_off[b], d_blk_x_off[b + 1]) of d_x (n_b of them) and rows
+ * [d_blk_z_off[b], d_blk_z_off[b + 1]) of d_z (m_b); an anchor is compared with its own block
+ * only.  blk_first / blk_count name the blocks the anchor range touches (naming more is
+ * harmless), max_n / max_m bound their n_b / m_b.  With q = a - a_begin:
+ *   "other" row  d_other[d_other_off[q] + k]  = D(x_a, z_k), k = 0 .. m_b - 1 (block-relative)
+ *   "own" row    d_own[d_own_off[q] + j']     = D(x_a, x_j), j != a, j' = j for j < a and j - 1
+ *                                               for j > a (block-relative): n_b - 1 entries
+ * The caller sizes d_other / d_own and packs the rows back to back, so that d_other_off /
+ * d_own_off (a_end - a_begin + 1 entries) are the d_x_off / d_z_off of tw_count_pairs or
+ * tw_count_pairs_sorted with one anchor per shard.  Blocks of any mix of sizes share the launch;
+ * no atomics, nothing to zero.  tw_triplet_rows_tile(): points per tile edge of the kernel.
+ *
+ * tw_triplet_idx32 counts given triplets: for p in [d_trip_off[s], d_trip_off[s + 1]), rows
+ * d_i[p], d_j[p] of d_x and d_k[p] of d_z (absolute, int32); d_out[s] (uint64) =
+ * #{D(x_i, z_k) > D(x_i, x_j)} for TW_PRED_GT, 2 #{>} + #{==} for TW_PRED_HALF (IEEE compares: a
+ * NaN distance counts for neither).  Block partials go through d_work
+ * (tw_triplet_idx_work_bytes bytes) and are added in a fixed order, as tw_self_pairs_idx32's.
+ *
+ * Argument errors (a null pointer, d outside [1, 64], a negative size, an empty anchor range,
+ * another predicate) return TW_ERR_ARG before any device work. */
+int32_t tw_triplet_rows_tile(void);
+int tw_triplet_rows(const double* d_x, const double* d_z, int32_t d, const int64_t* d_blk_x_off,
+                    const int64_t* d_blk_z_off, int32_t blk_first, int32_t blk_count,
+                    int64_t a_begin, int64_t a_end, int64_t max_n, int64_t max_m,
+                    const int64_t* d_other_off, const int64_t* d_own_off, double* d_other,
+                    double* d_own, void* stream);
+int64_t tw_triplet_idx_work_bytes(int32_t n_shards, int64_t max_triplets);
+int tw_triplet_idx32(const double* d_x, const double* d_z, int32_t d, const int32_t* d_i,
+                     const int32_t* d_j, const int32_t* d_k, const int64_t* d_trip_off,
+                     int32_t n_shards, int64_t max_triplets, int32_t pred, void* d_work,
+                     uint64_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

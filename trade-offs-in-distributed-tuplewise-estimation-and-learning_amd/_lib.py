@@ -252,6 +252,11 @@ _SIGNATURES = {
     "tw_self_sorted": [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
     "tw_count_chain_class_form": [_i32, _i32],
     "tw_count_chain_class_span": [_i32],
+    "tw_triplet_rows_tile": [],
+    "tw_triplet_rows": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp,
+                        _vp, _vp, _vp],
+    "tw_triplet_idx_work_bytes": [_i32, _i64],
+    "tw_triplet_idx32": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -273,6 +278,7 @@ _RESTYPES = {
     "tw_self_pairs_idx_work_bytes": ctypes.c_int64,
     "tw_self_sorted_work_bytes": ctypes.c_int64,
     "tw_chain_planes_work_bytes": ctypes.c_int64,
+    "tw_triplet_idx_work_bytes": ctypes.c_int64,
 }
 
 _lib = None

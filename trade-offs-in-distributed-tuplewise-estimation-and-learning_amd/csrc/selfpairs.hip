@@ -12,6 +12,7 @@
 // second kernel adds a shard's partials in a fixed order — the Kendall integers the same way
 // (no atomics, nothing to zero).
 #include "tw_common.h"
+#include "selfreduce.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -82,25 +83,6 @@ __device__ __forceinline__ double self_fkern(double si, double sj) {
   const double d = si - sj;
   if constexpr (K == TW_SELF_GINI) return fabs(d);
   else return d * d;  // halved once per block partial (an exact scaling)
-}
-
-__device__ __forceinline__ double self_block_sum_f64(double v, double* part) {
-  v = wave_sum_f64(v);
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  __syncthreads();  // part's previous readers
-  if (lane == 0) part[wid] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-__device__ __forceinline__ unsigned long long self_block_sum_u64(unsigned long long v,
-                                                                 unsigned long long* part) {
-  v = wave_sum_u64(v);
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  __syncthreads();
-  if (lane == 0) part[wid] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
 }
 
 // Block `blockIdx.x` = (shard, group of kSelfG consecutive tile pairs of the triangle).
@@ -256,25 +238,6 @@ __global__ __launch_bounds__(kBlock) void k_self_pairs_idx(const V* __restrict__
   } else {
     const double b = self_block_sum_f64(fa, (double*)part);
     if (threadIdx.x == 0) ((double*)work)[blockIdx.x] = K == TW_SELF_VAR ? 0.5 * b : b;
-  }
-}
-
-// out[s][k] = ordered sum of work[s * per + i][k], i < per: one block per shard, lane-strided
-// partial sums in a fixed order, then the fixed butterfly and wave order of the block sums.
-template <typename A, int W>
-__global__ __launch_bounds__(kBlock) void k_self_reduce(const A* __restrict__ work, int per,
-                                                        A* __restrict__ out) {
-  __shared__ unsigned long long part[kBlock / kWave];
-  const A* __restrict__ w = work + (int64_t)blockIdx.x * per * W;
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    A v = A(0);
-#pragma unroll 4
-    for (int i = threadIdx.x; i < per; i += kBlock) v += w[(int64_t)i * W + k];
-    A b;
-    if constexpr (std::is_floating_point<A>::value) b = self_block_sum_f64(v, (double*)part);
-    else b = self_block_sum_u64(v, part);
-    if (threadIdx.x == 0) out[(int64_t)blockIdx.x * W + k] = b;
   }
 }
 
