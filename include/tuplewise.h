@@ -238,6 +238,18 @@ int32_t tw_count_chain_class_form(int32_t nb, int32_t k);
  * other value changes nothing.  Returns the setting in force before the call.  Process-global;
  * same counts; the masked-plane loop (form 2) always runs one entry per item. */
 int32_t tw_count_chain_class_span(int32_t runs);
+/* A/B control of the digit loop's split: planes per digit.  4 runs the wide
+ * digits — three tables of 16 (+ 1) entries, 4 VALU and 5 SALU per z image and group instead
+ * of 5 and 7 — where nb - k = 12 and the four-digit loop anywhere else; 3 forces the four-digit
+ * loop everywhere; 0 restores the automatic rule (chainclass.h kClassDigitsAuto: wide where it
+ * fits); -1 only reports.  Returns the setting in force before the call (0, 3 or 4); any other
+ * value changes nothing and returns TW_ERR_ARG.  Process-global; same counts, same workspace:
+ * every launch re-encodes its z region for the loop it runs. */
+int32_t tw_count_chain_class_digits(int32_t w);
+/* The planes per digit a count with nb planes and k class bits runs under the current setting:
+ * 4 where it runs the wide digits, 3 anywhere else (where the launch runs no digit loop — see
+ * tw_count_chain_class_form — the setting has no effect). */
+int32_t tw_count_chain_class_digits_of(int32_t nb, int32_t k);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
  * estimation-experiment/main.py:29-31's integer): each bag's z images (integers in
  * [0, z_total], z_total = the Z count the images were ranked against) counting-sorted into

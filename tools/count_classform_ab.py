@@ -17,7 +17,14 @@ tables, with R groups per item; default: every library present)
 under the automatic class bits and swap rule, tw_count_chain_class_span forced to 1, 2, 4, 8,
 16, 32 and the whole bag, and the automatic rule, interleaved over the rounds; per shape and
 span the median, min and max ms, the ratio of medians to M = 1 of the same process, and M = 1's
-own spread (max - min) / median, against which a shape's automatic setting is judged."""
+own spread (max - min) / median, against which a shape's automatic setting is judged.
+
+--digits [out.json]: the digit-width sweep of DESIGN §4.1k, same shapes, product library, one
+process per pass: under the automatic class bits, swap rule and span, tw_count_chain_class_digits
+forced to 3 (the four-digit loop), to 4 (the wide digits where NB - K = 12) and automatic,
+interleaved over the rounds; per shape the ratio of medians of the whole native call to the
+four-digit loop and the four-digit loop's own spread.  Shapes whose automatic class bits leave a
+low field other than 12 planes run the same kernel under every setting."""
 import json
 import os
 import pathlib
@@ -33,6 +40,8 @@ SETTINGS = [("k=0", 0, 1, 0), ("automatic", -1, 1, 0), ("automatic, swap 0", -1,
 WHOLE_BAG = 1 << 20  # (clamped to the launch's table capacity)
 SPAN_SETTINGS = [("M=1", -1, 1, 1)] + [(f"M={m}", -1, 1, m) for m in (2, 4, 8, 16, 32)] + [
     ("M=whole bag", -1, 1, WHOLE_BAG), ("automatic", -1, 1, 0)]
+# (name, class bits, swap, span, planes per digit)
+DIGIT_SETTINGS = [("digits=3", -1, 1, 0, 3), ("digits=4", -1, 1, 0, 4), ("automatic", -1, 1, 0, 0)]
 # (name, G, K): G ranks share the strong problem; G = 0: C2; G = -1: 64 bags per step of
 # 7 * 2048 + 100 x images, a remainder small enough that class_swap_mode keeps it swapped
 SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1, 4),
@@ -74,7 +83,8 @@ def child(settings=SETTINGS, base="k=0"):
                    out, L.stream_handle(), work, wb)
         try:
             for _ in range(ROUNDS):
-                for sname, bits, swap, span in settings:
+                for sname, bits, swap, span, *digits in settings:
+                    assert L.lib().tw_count_chain_class_digits(digits[0] if digits else 0) != 1
                     L.call("tw_count_chain_set_class_bits", bits)
                     L.call("tw_count_chain_set_swap", swap)
                     L.lib().tw_count_chain_class_span(span)
@@ -93,6 +103,7 @@ def child(settings=SETTINGS, base="k=0"):
             L.call("tw_count_chain_set_class_bits", -1)
             L.call("tw_count_chain_set_swap", 1)
             L.lib().tw_count_chain_class_span(0)
+            L.lib().tw_count_chain_class_digits(0)
         ms = {s: {"median": float(np.median(t)), "min": float(min(t)), "max": float(max(t))}
               for s, t in ts.items()}
         report.append({"shape": name, "bags": K * Nl, "nx": k, "nz": kz, "ms": ms,
@@ -101,14 +112,18 @@ def child(settings=SETTINGS, base="k=0"):
     print(json.dumps(report))
 
 
-def spans_main():
-    """One child per pass, the product library: the span sweep."""
+def spans_main(flag="--spans-child", settings=SPAN_SETTINGS, base="M=1",
+               what="tw_count_pairs_chain_planes under forced spans (tw_count_chain_class_span)"
+                    " and the automatic rule: ms of the whole native call and the ratio of "
+                    "medians to M = 1 inside each child; one child per pass"):
+    """One child per pass, the product library: the span sweep (or, with the arguments of
+    --digits, the digit-width sweep)."""
     out = sys.argv[2] if len(sys.argv) > 2 else None
     env = dict(os.environ)
     env.pop("TW_LIB_PATH", None)
     passes = []
     for rep in range(REPS):
-        r = subprocess.run([sys.executable, __file__, "--spans-child"], env=env,
+        r = subprocess.run([sys.executable, __file__, flag], env=env,
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             print("failed:", r.stderr[-1500:], flush=True)
@@ -116,14 +131,12 @@ def spans_main():
         rows = json.loads(r.stdout.strip().splitlines()[-1])
         passes.append(rows)
         for row in rows:
-            print(f"pass {rep} {row['shape']}: spread of M=1 {row['spread of M=1']:.4f}  " + "  ".join(
-                f"{s[0]} {row['ratio to M=1'][s[0]]:.4f}" for s in SPAN_SETTINGS[1:]), flush=True)
+            print(f"pass {rep} {row['shape']}: spread of {base} {row[f'spread of {base}']:.4f}  "
+                  + "  ".join(f"{s[0]} {row[f'ratio to {base}'][s[0]]:.4f}" for s in settings[1:]),
+                  flush=True)
         if out:
-            pathlib.Path(out).write_text(json.dumps(
-                {"what": "tw_count_pairs_chain_planes under forced spans (tw_count_chain_class_span)"
-                         " and the automatic rule: ms of the whole native call and the ratio of "
-                         "medians to M = 1 inside each child; one child per pass",
-                 "passes": passes}, indent=1) + "\n")
+            pathlib.Path(out).write_text(json.dumps({"what": what, "passes": passes},
+                                                    indent=1) + "\n")
 
 
 def main():
@@ -164,5 +177,13 @@ if __name__ == "__main__":
         child(SPAN_SETTINGS, "M=1")
     elif sys.argv[1:2] == ["--spans"]:
         spans_main()
+    elif sys.argv[1:2] == ["--digits-child"]:
+        child(DIGIT_SETTINGS, "digits=3")
+    elif sys.argv[1:2] == ["--digits"]:
+        spans_main("--digits-child", DIGIT_SETTINGS, "digits=3",
+                   "tw_count_pairs_chain_planes under tw_count_chain_class_digits 3, 4 and the "
+                   "automatic rule (automatic class bits, swap and span): ms of the whole native "
+                   "call and the ratio of medians to the four-digit loop inside each child; one "
+                   "child per pass")
     else:
         main()

@@ -252,6 +252,8 @@ _SIGNATURES = {
     "tw_self_sorted": [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
     "tw_count_chain_class_form": [_i32, _i32],
     "tw_count_chain_class_span": [_i32],
+    "tw_count_chain_class_digits": [_i32],
+    "tw_count_chain_class_digits_of": [_i32, _i32],
     "tw_triplet_rows_tile": [],
     "tw_triplet_rows": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp,
                         _vp, _vp, _vp],

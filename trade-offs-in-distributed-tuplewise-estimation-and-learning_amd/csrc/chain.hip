@@ -655,7 +655,8 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_planes(
 // passes over the images in global memory (histogram; scatter through LDS cursors), so a bag
 // of any size goes through; the order inside a class is that of the cursors' atomics, which
 // the counts — integer sums — do not see.  With cp.digits > 0 (the digit loop)
-// an image is stored digit-ready (class_digit_encode): one word per image either way.
+// an image is stored digit-ready (class_digit_encode; class_wide_encode where cp.dbits asks for
+// the wide digits of §4.1k): one word per image either way, written anew by every launch.
 __device__ __forceinline__ uint32_t class_block_scan(uint32_t v, uint32_t* wsum, int lane,
                                                      int wid) {
 #pragma unroll
@@ -716,7 +717,9 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
       const uint32_t zc = bits_z_image(f[u]);
       if (i0 + u * kBlock < nz)
         zs[atomicAdd(&hist[class_of(zc, nb, cp.k)], 1u)] =  // < c0 + n <= nz
-            cp.digits > 0 ? class_digit_encode(zc, cp.digits) : zc;
+            cp.digits <= 0                 ? zc
+            : cp.dbits == kClassWideBits ? class_wide_encode(zc)
+                                         : class_digit_encode(zc, cp.digits);
     }
   }
 }
@@ -733,7 +736,13 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
 // of the joint kernel.  Where the low field fits the digit tables (form 3, DESIGN
 // §4.1i, §4.1j) the runs' images are digit-ready and the item runs bits_count_span_digits: 122
 // VGPRs at NL = 12 (4 waves), 96 at narrower low fields (5 waves), as before the spans.
-template <int NB, int K>
+//  DW is the digit loop's planes per digit.  DW = kClassWideBits exists for
+// NB - K = 12 alone — (16, 4), (18, 6), (20, 8) — and runs bits_count_span_wide on images
+// pre-pass 2 wrote with class_wide_encode (cp.dbits): three 4-plane digits, 8 VALU + 5 SALU per
+// z at two groups instead of 10 + 7, 124 - 126 VGPRs, no scratch, 4 waves.  The launcher picks
+// it under tw_count_chain_class_digits' setting (automatic: wherever it fits); every other
+// instantiation is the four-digit or masked-plane kernel it was, register for register.
+template <int NB, int K, int DW = kClassDigitBits>
 __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
     const int64_t* __restrict__ x_off, const int64_t* __restrict__ z_off, int n_shards,
     int n_bags, PlanesPlan p, ClassPlan cp, const uint32_t* __restrict__ work,
@@ -768,6 +777,13 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
           work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride);
       unsigned long long t;
 #if TW_CLASS_FORM == 3
+#if TW_CLASS_WIDE
+      if constexpr (DW == kClassWideBits) {  // the wide-digit loop: NB - K = 12, R <= 2
+        static_assert(class_wide_built(NB, K), "the wide digits take the 12-plane low field");
+        t = bits_count_span_wide_of<NB, K, kClassDigitsMaxR>(pw, zbag, tab, sp.e1 - sp.e0, lane,
+                                                             ng);
+      } else
+#endif
       if constexpr (class_loop_form(NB, K) == 3) {  // the digit loop: the launcher planned
         t = bits_count_span_digits_of<NB, K, kClassDigitsMaxR>(  // R <= kClassDigitsMaxR
             pw, zbag, tab, sp.e1 - sp.e0, lane, ng);
@@ -979,6 +995,7 @@ static int64_t g_chain_zchunk = 0;
 static int g_planes_swap = 1;  // (tw_count_chain_set_swap: 0 never, 1 automatic, 2 always)
 static int g_class_bits = -1;  // (tw_count_chain_set_class_bits: -1 automatic, 0 off, 1..8)
 static int g_class_span = 0;   // (tw_count_chain_class_span: 0 automatic, >= 1 entries per item)
+static int g_class_digits = 0;  // (tw_count_chain_class_digits: 0 automatic, 3 or 4 planes)
 
 // strict: R in {16, 8} x-images per lane, least padded slots (ties to 16); half: R = 8 {g, h}
 // pairs (the same 8 packed registers per lane).  z chunks: as many as give ~150 work items per
@@ -1535,6 +1552,13 @@ static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, 
         b(kBlock);
 #define TW_CLASS_CASE(K)                                                                       \
   case K:                                                                                      \
+    if constexpr (class_wide_built(NB, K)) {                                                   \
+      if (cp.dbits == kClassWideBits) {                                                        \
+        hipLaunchKernelGGL((k_count_chain_classes<NB, K, kClassWideBits>), g, b, 0, st,        \
+                           d_x_off, d_z_off, n_shards, bags, p, cp, (const uint32_t*)work, o); \
+        break;                                                                                 \
+      }                                                                                        \
+    }                                                                                          \
     hipLaunchKernelGGL((k_count_chain_classes<NB, K>), g, b, 0, st, d_x_off, d_z_off,          \
                        n_shards, bags, p, cp, (const uint32_t*)work, o);                       \
     break;
@@ -1584,11 +1608,15 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   const bool digits = k > 0 && class_loop_form(nb, k) == 3;
   int R = g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0;
   if (digits) R = R == 0 || R > kClassDigitsMaxR ? kClassDigitsMaxR : R;
+  // planes per digit: the wide split where this build has it and the hook's setting asks for it
+  const int dbits = digits && class_wide_built(nb, k) ? class_digit_bits(nb, k, g_class_digits)
+                                                      : kClassDigitBits;
+  const int ndigits = dbits == kClassWideBits ? kClassWideDigits : kClassDigits;
   // (a padded slot's price in the swap rule is that of the loop this launch runs)
   const PlanesPlan p =
       planes_plan(max_nx, max_nz, bags, R, g_chain_zchunk,
                   class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k,
-                                  digits ? kClassDigits + 1 : 0));
+                                  digits ? ndigits + 1 : 0));
   // entries per item: the digit loop walks a span (forced, or chainclass.h's automatic rule);
   // the masked-plane loop's registers are class-dependent throughout: one run per item
   int64_t runs = 1;
@@ -1598,6 +1626,7 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
                : class_span_auto(bags, p.tiles_x, (int)class_capacity(max_nz, k, p.z_chunk));
   ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k, runs);
   cp.digits = digits ? nb - k : 0;
+  cp.dbits = digits ? dbits : 0;
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
                    bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&
                    bags * (int64_t)cp.per_bag < (1ll << 31),
@@ -1639,6 +1668,27 @@ extern "C" int32_t tw_count_chain_class_span(int32_t runs) {
   const int32_t before = g_class_span;
   if (runs >= 0) g_class_span = runs;
   return before;
+}
+
+// The planes per digit of the digit loop (chainclass.h): 0 the automatic rule, 3
+// the four-digit loop everywhere, 4 the wide digits where NB - K = 12 (anywhere else the
+// four-digit loop runs), -1 only reports.  Returns the setting in force before the call;
+// anything else changes nothing and returns TW_ERR_ARG.
+extern "C" int32_t tw_count_chain_class_digits(int32_t w) {
+  const int32_t before = g_class_digits;
+  if (w == -1) return before;
+  TW_ARG_CHECK(w == 0 || w == kClassDigitBits || w == kClassWideBits,
+               "tw_count_chain_class_digits: 0 (automatic), 3, 4 or -1 (report)");
+  g_class_digits = w;
+  return before;
+}
+
+// The planes per digit a launch of (nb, k) runs under the current setting: 4 where it runs the
+// wide digits, 3 everywhere else (where no digit loop runs the setting has no effect)
+extern "C" int32_t tw_count_chain_class_digits_of(int32_t nb, int32_t k) {
+  return k > 0 && class_loop_form(nb, k) == 3 && class_wide_built(nb, k)
+             ? class_digit_bits(nb, k, g_class_digits)
+             : kClassDigitBits;
 }
 
 extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,

@@ -195,6 +195,83 @@ TW_BITS_HD ClassMasked class_gt32_digits(const ClassDigitTables& t, uint32_t G, 
   return ClassMasked{G, c};
 }
 
+// -------------------------------------------------------------------- the wide digit tables
+// A second split for the widest low field: NL = 12 as kClassWideDigits digits of
+// kClassWideBits planes instead of four of three — one table step and one shift + index less per
+// z image, for tables of 2^4 (+ 1) entries: 16 + 17 + 17 = 50 registers per group instead of 35.
+// Same arithmetic (class_digit_table<4>), same contract: the top digit is built under E with
+// entry 16 = E, digit 0 needs no entry 16.  Narrower low fields stay on the split above.
+constexpr int kClassWideDigits = 3;
+constexpr int kClassWideBits = 4;
+constexpr int kClassWideNL = kClassWideDigits * kClassWideBits;
+constexpr int kClassWideEntries = (1 << kClassWideBits) + 1;
+// a low field the wide tables take
+constexpr bool class_wide_fit(int nl) { return nl == kClassWideNL; }
+// table entries per group: 16 of digit 0, 17 of digits 1 and 2
+constexpr int class_wide_table_regs() {
+  return (1 << kClassWideBits) + (kClassWideDigits - 1) * kClassWideEntries;
+}
+// The device loop's register map (R <= kClassWideMaxR groups): group g's tables from
+// v(kClassWideBase + 50 g), entry d of digit j at flat register class_wide_reg(j, d) inside it
+// — digit 0 at + 0, digits 1 and 2 at + 16 and + 33 — so two groups end at v123.
+constexpr int kClassWideBase = 24, kClassWideMaxR = 2;
+constexpr int kClassWideGroupRegs = class_wide_table_regs();
+constexpr int class_wide_reg(int j, int d) {
+  return j == 0 ? d : (1 << kClassWideBits) + kClassWideEntries * (j - 1) + d;
+}
+constexpr int class_wide_group_base(int g) { return kClassWideBase + kClassWideGroupRegs * g; }
+constexpr int class_wide_last_reg(int groups) { return class_wide_group_base(groups) - 1; }
+
+// The digit-ready word of the wide split: digit j in byte j, bytes 0 .. 2 used, byte 3 zero.
+// Every digit is masked to kClassWideBits bits here and again in class_wide_of: no index leaves
+// a 17-entry table (the loop reads entries d and d + 1 <= 16).
+TW_BITS_HD uint32_t class_wide_encode(uint32_t zc) {
+  uint32_t w = 0;
+  for (int j = 0; j < kClassWideDigits; ++j)
+    w |= ((zc >> (kClassWideBits * j)) & ((1u << kClassWideBits) - 1u)) << (8 * j);
+  return w;
+}
+TW_BITS_HD uint32_t class_wide_of(uint32_t word, int j) {
+  return (word >> (8 * j)) & ((1u << kClassWideBits) - 1u);
+}
+
+// The tables of one x group: entry d of digit j at g[j][d], d = 0 .. 16 (g[0][16] is never read)
+struct ClassWideTables {
+  uint32_t g[kClassWideDigits][kClassWideEntries];
+};
+// digit J of the group's UNMASKED low planes; E as in class_digit_tables_one
+template <int J>
+TW_BITS_HD void class_wide_tables_one(const uint32_t (&low)[kClassWideNL], uint32_t E,
+                                      ClassWideTables& t) {
+  uint32_t pl[kClassWideBits];
+#pragma unroll
+  for (int b = 0; b < kClassWideBits; ++b) pl[b] = low[kClassWideBits * J + b];
+  class_digit_table<kClassWideBits>(pl, J == kClassWideDigits - 1 ? E : ~0u, t.g[J]);
+}
+TW_BITS_HD void class_wide_tables(const uint32_t (&low)[kClassWideNL], uint32_t E,
+                                  ClassWideTables& t) {
+  class_wide_tables_one<0>(low, E, t);
+  class_wide_tables_one<1>(low, E, t);
+  class_wide_tables_one<2>(low, E, t);
+}
+// class_gt32_masked by the wide tables: word is a z image's class_wide_encode
+TW_BITS_HD ClassMasked class_gt32_wide(const ClassWideTables& t, uint32_t G, uint32_t word) {
+  uint32_t c = t.g[0][class_wide_of(word, 0)];
+  for (int j = 1; j < kClassWideDigits; ++j) {
+    const uint32_t d = class_wide_of(word, j);
+    c = bits_carry(t.g[j][d], t.g[j][d + 1], c);
+  }
+  return ClassMasked{G, c};
+}
+// The digit width a launch of (nb, k) runs under the hook's setting (0 automatic, 3, 4) where
+// it runs a digit loop at all: kClassWideBits only at the widest low field, kClassDigitBits at
+// every other.  Automatic: the wide digits wherever they fit (sweep: DESIGN §4.1k).
+constexpr int kClassDigitsAuto = kClassWideBits;
+TW_BITS_HD int class_digit_bits(int nb, int k, int setting) {
+  const int want = setting == 0 ? kClassDigitsAuto : setting;
+  return want == kClassWideBits && class_wide_fit(nb - k) ? kClassWideBits : kClassDigitBits;
+}
+
 // ---------------------------------------------------------------------------- the run table
 // Per bag: for each non-empty class, ceil(n_c / chunk) runs of near-equal length over the
 // class's range of the class-ordered region, classes in ascending order.  An entry is two u32
@@ -310,6 +387,9 @@ struct ClassPlan {
   int digits;  // > 0: pre-pass 2 writes the images digit-ready for this many low planes (the
                // launcher sets it for the digit loop; same words, same regions)
   int span;    // table entries an item walks (1 .. cap; the masked-plane loop: always 1)
+  int dbits;   // planes per digit of the launch's digit loop: kClassWideBits under the wide
+               // loop (pre-pass 2 then writes class_wide_encode), anything else the four-digit
+               // split (the launcher sets it; class_plan leaves 0)
 };
 
 // A lane's u32 sums over a span — its popcounts, at most 32 per image and group, and
@@ -363,7 +443,8 @@ TW_BITS_HD int class_bits_auto(int64_t max_nz, int64_t n_bags, int nb) {
 // 0.93-0.95 of the swapped launch's time; a remainder of a few images stays
 // swapped.  Forced settings and launches without classes are left alone.
 // slot_valu: what a padded slot costs per z and group in the loop the launch runs — 0 stands
-// for the masked-plane loop's NL + 1; the digit loop passes kClassDigits + 1.
+// for the masked-plane loop's NL + 1; the digit loop passes kClassDigits + 1,
+// the wide-digit loop kClassWideDigits + 1 (§4.1k: neither decision of the sweep moved).
 TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb, int k,
                                int slot_valu = 0) {
   if (k == 0 || swap != 1) return swap;
@@ -755,7 +836,205 @@ __device__ __forceinline__ unsigned long long bits_count_span_digits_of(
     if (ng < R) return bits_count_span_digits_of<NB, K, R - 1>(pw, zbag, tab, n, lane, ng);
   return bits_count_span_digits<NB, K, R>(pw, zbag, tab, n, lane);
 }
+
+// The wide-digit loop: bits_count_span_digits on the three 4-plane digits of a
+// 12-plane low field (class_wide_*), built where the register map holds the groups of an item
+// (TW_CLASS_DIGIT_R <= kClassWideMaxR).  Per z the scalar side shifts the word twice and sets the
+// index three times (5 SALU, not 7); per z and group the lane side issues one v_mov, two
+// v_bitop3 and one v_bcnt (4 VALU, not 5).  Register map: v8 .. v15 the carries of a batch
+// (image u, group g: v(8 + 2u + g)); group g's 50 table registers from v(24 + 50g): digit 0 at
+// + 0 (16 entries), digits 1 and 2 at + 16 and + 33 (17 entries each); two groups end at v123.
+// Only words pre-pass 2 wrote with class_wide_encode reach M0: every digit is below 16, so an
+// indexed read of entries d and d + 1 stays inside its table.
+#define TW_CLASS_WIDE (TW_CLASS_DIGIT_R <= 2)
+#if TW_CLASS_WIDE
+typedef uint32_t ClassVec2 __attribute__((ext_vector_type(2)));
+typedef uint32_t ClassVec16 __attribute__((ext_vector_type(16)));
+static_assert(kClassDigitsMaxR <= kClassWideMaxR, "the wide register map holds two groups");
+static_assert(class_wide_group_base(0) == 24 && class_wide_group_base(1) == 74 &&
+                  class_wide_last_reg(2) == 123,
+              "the registers named below");
+static_assert(class_wide_reg(1, 0) == 40 - 24 && class_wide_reg(2, 0) == 57 - 24 &&
+                  class_wide_reg(2, 16) == 73 - 24,
+              "the registers named below");
+#define TW_WD_D0_1(C0, C1) TW_DG_MOV(C0, "v24")
+#define TW_WD_D0_2(C0, C1) TW_WD_D0_1(C0, C1) TW_DG_MOV(C1, "v74")
+#define TW_WD_D1_1(C0, C1) TW_DG_OP(C0, "v40", "v41")
+#define TW_WD_D1_2(C0, C1) TW_WD_D1_1(C0, C1) TW_DG_OP(C1, "v90", "v91")
+#define TW_WD_D2_1(C0, C1) TW_DG_OP(C0, "v57", "v58")
+#define TW_WD_D2_2(C0, C1) TW_WD_D2_1(C0, C1) TW_DG_OP(C1, "v107", "v108")
+// one image against R groups; the index already holds its digit 0
+#define TW_WD_Z(R, Z, T, C0, C1)                                \
+  TW_WD_D0_##R(C0, C1)                                          \
+  TW_DG_IDX(Z, T, "8") TW_WD_D1_##R(C0, C1)                     \
+  TW_DG_IDX(Z, T, "16") TW_WD_D2_##R(C0, C1)
+#define TW_WD_C_1(C0, C1) TW_DG_CNT(C0, "%[a0]")
+#define TW_WD_C_2(C0, C1) TW_WD_C_1(C0, C1) TW_DG_CNT(C1, "%[a1]")
+#define TW_WD_ONE(R)                                            \
+  "s_set_gpr_idx_on %[z0], 0x3\n\t"                             \
+  TW_WD_Z(R, "%[z0]", "%[t]", "v8", "v9") "s_set_gpr_idx_off\n\t" TW_WD_C_##R("v8", "v9")
+#define TW_WD_BATCH(R)                                                        \
+  "s_load_dwordx4 %[nx], %[p], 0x0\n\ts_set_gpr_idx_on %[z0], 0x3\n\t"        \
+  TW_WD_Z(R, "%[z0]", "%[t]", "v8", "v9") "s_set_gpr_idx_idx %[z1]\n\t"      \
+  TW_WD_Z(R, "%[z1]", "%[t]", "v10", "v11") "s_set_gpr_idx_idx %[z2]\n\t"    \
+  TW_WD_Z(R, "%[z2]", "%[t]", "v12", "v13") "s_set_gpr_idx_idx %[z3]\n\t"    \
+  TW_WD_Z(R, "%[z3]", "%[t]", "v14", "v15") "s_set_gpr_idx_off\n\t"          \
+  TW_WD_C_##R("v8", "v9") TW_WD_C_##R("v10", "v11")                          \
+  TW_WD_C_##R("v12", "v13") TW_WD_C_##R("v14", "v15")                        \
+  "s_waitcnt lgkmcnt(0)"
+#define TW_WD_CARRIES1 "scc", "v8", "v9"
+#define TW_WD_CARRIES4 TW_WD_CARRIES1, "v10", "v11", "v12", "v13", "v14", "v15"
+#define TW_WD_TAB_1(a, b, c) "{v[24:55]}"(a[0]), "{v[56:71]}"(b[0]), "{v[72:73]}"(c[0])
+#define TW_WD_TAB_2(a, b, c) \
+  TW_WD_TAB_1(a, b, c), "{v[74:105]}"(a[1]), "{v[106:121]}"(b[1]), "{v[122:123]}"(c[1])
+#define TW_WD_CASE_BATCH(R)                                                                \
+  if constexpr (kR == R)                                                                   \
+    asm volatile(TW_WD_BATCH(R)                                                            \
+                 : TW_DG_ACC_##R(acc), [t] "=&s"(t), [nx] "=&s"(next)                      \
+                 : [z0] "s"(z[0]), [z1] "s"(z[1]), [z2] "s"(z[2]), [z3] "s"(z[3]),         \
+                   [p] "s"(nz), TW_WD_TAB_##R(ta, tb, tc)                                  \
+                 : TW_WD_CARRIES4);
+#define TW_WD_CASE_ONE(R)                                                                  \
+  if constexpr (kR == R)                                                                   \
+    asm volatile(TW_WD_ONE(R)                                                              \
+                 : TW_DG_ACC_##R(acc), [t] "=&s"(t)                                        \
+                 : [z0] "s"(z), TW_WD_TAB_##R(ta, tb, tc)                                  \
+                 : TW_WD_CARRIES1);
+
+// The class count of one item under the wide-digit loop: bits_count_span_digits' contract and
+// statement structure — whole batches of four images per asm statement, each loading the batch
+// after it; the last len mod 4 images one statement each from the batch already loaded, so
+// exactly len images are evaluated and no word past a run's end reaches M0.  Once per item:
+// digit tables 0 and 1.  The K top planes and the top digit's four planes are reloaded per new
+// class (cache hits; the opaque lane index keeps the reloads inside the span): keeping them
+// would cost the fourth wave per SIMD.  The per-class rebuild writes the top digit's entries
+// 1 .. 16 in place; entry 0 stays 0.
+template <int NB, int K, int R>
+__device__ __forceinline__ unsigned long long bits_count_span_wide(
+    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zbag,
+    const uint32_t* __restrict__ tab, int n, int lane) {
+  constexpr int NL = NB - K;
+  static_assert(class_wide_fit(NL), "the wide split is that of the 12-plane low field");
+  constexpr int kTop = kClassWideDigits - 1;  // the digit whose planes are ANDed with E
+  constexpr int W = kClassWideBits, S = W * kTop;
+  [[maybe_unused]] constexpr int kR = R;
+  static_assert(R >= 1 && R <= kClassWideMaxR, "the register map holds kClassWideMaxR groups");
+  ClassVec32 ta[R];
+  ClassVec16 tb[R];
+  ClassVec2 tc[R];
+  uint32_t acc[R];
+  auto place = [&](int r, int j, int d, uint32_t v) {
+    const int f = class_wide_reg(j, d);
+    if (f < 32)
+      ta[r][f] = v;
+    else if (f < 48)
+      tb[r][f - 32] = v;
+    else
+      tc[r][f - 48] = v;
+  };
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    uint32_t low[NL];
+#pragma unroll
+    for (int b = 0; b < S; ++b) low[b] = pw[(r * NB + b) * 64 + lane];
+#pragma unroll
+    for (int b = S; b < NL; ++b) low[b] = 0u;  // (the top digit's planes: per class)
+    ClassWideTables t;
+    class_wide_tables_one<0>(low, ~0u, t);
+    class_wide_tables_one<1>(low, ~0u, t);
+    ta[r] = 0u, tb[r] = 0u, tc[r] = 0u;
+#pragma unroll
+    for (int j = 0; j < kTop; ++j)
+#pragma unroll
+      for (int d = 0; d < (j == 0 ? 1 << W : kClassWideEntries); ++d) place(r, j, d, t.g[j][d]);
+    acc[r] = 0;
+  }
+  typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+  const ConstWords ct = (ConstWords)(uintptr_t)tab;
+  const ConstWords zc = (ConstWords)(uintptr_t)zbag;
+  // z: the four images to evaluate; the statement loads the four words at nz into next
+  auto batch = [&](const ClassVec4 z, ConstWords nz, ClassVec4& next) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t t;
+    TW_WD_CASE_BATCH(1) TW_WD_CASE_BATCH(2)
+#else
+    next = z;
+#endif
+  };
+  auto one = [&](uint32_t z) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t t;
+    TW_WD_CASE_ONE(1) TW_WD_CASE_ONE(2)
+#endif
+  };
+  uint32_t ng = 0, cg = 0;  // popc(G) over the groups of the class at hand; sum of len * ng
+  uint32_t cls = ~0u;       // (no class)
+  for (int e = 0; e < n; ++e) {
+    const ClassRun run = class_entry(ct[2 * e], ct[2 * e + 1]);
+    if (run.cls != cls) {  // wave-uniform
+      cls = run.cls;
+      ng = 0;
+      int ql = lane;  // (opaque per class: the reloads are not hoisted out of the span)
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" : "+v"(ql));
+#endif
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        uint32_t G, P, g[kClassWideEntries], tp[K], hp[W];
+#pragma unroll
+        for (int b = 0; b < K; ++b) tp[b] = pw[(r * NB + NL + b) * 64 + ql];
+#pragma unroll
+        for (int b = 0; b < W; ++b) hp[b] = pw[(r * NB + S + b) * 64 + ql];
+        class_gp<K>(tp, cls, G, P);
+        ng = bits_popc_add(G, ng);
+        class_digit_table<W>(hp, class_equal_mask(G, P), g);
+#pragma unroll
+        for (int d = 1; d <= (1 << W); ++d) place(r, kTop, d, g[d]);  // (entry 0 stays 0)
+      }
+    }
+    const int len = (int)run.len;  // >= 1: only non-empty classes have runs
+    cg += (uint32_t)len * ng;      // the run's exact length
+    ConstWords p = zc + run.z0;
+    ClassVec4 a, b;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[u] = p[u];
+    int j = 0;
+    for (; j + 8 <= len; j += 8, p += 8) {
+      batch(a, p + 4, b);
+      batch(b, p + 8, a);
+    }
+    if (j + 4 <= len) {
+      batch(a, p + 4, b);
+      a = b, j += 4;
+    }
+    for (; j < len; ++j) {  // a holds the images from j on: never a word past the run's end
+      one(a[0]);
+      a = a.yzww;
+    }
+  }
+  unsigned long long tot = cg;
+#pragma unroll
+  for (int r = 0; r < R; ++r) tot += acc[r];
+  return tot;
+}
+template <int NB, int K, int R>
+__device__ __forceinline__ unsigned long long bits_count_span_wide_of(
+    const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zbag,
+    const uint32_t* __restrict__ tab, int n, int lane, int ng) {
+  if constexpr (R > 1)
+    if (ng < R) return bits_count_span_wide_of<NB, K, R - 1>(pw, zbag, tab, n, lane, ng);
+  return bits_count_span_wide<NB, K, R>(pw, zbag, tab, n, lane);
+}
+#endif  // TW_CLASS_WIDE
 #endif  // TW_CLASS_FORM == 3
+// Whether this build has the wide-digit loop for a launch of (nb, k)
+constexpr bool class_wide_built(int nb, int k) {
+#if TW_CLASS_FORM == 3 && TW_CLASS_DIGIT_R <= 2
+  return class_wide_fit(nb - k);
+#else
+  return false;
+#endif
+}
 #endif  // __HIPCC__
 
 }  // namespace tw
