@@ -1243,6 +1243,46 @@ int tw_triplet_idx32(const double* d_x, const double* d_z, int32_t d, const int3
                      int32_t n_shards, int64_t max_triplets, int32_t pred, void* d_work,
                      uint64_t* d_out, void* stream);
 
+/* ---- Triplet metric learning (csrc/triplet_grad.hip; tuplewise.triplet_learning; DESIGN.md
+ * §4.11; an extension, not in the reference): a linear map d_L (p, d) float64 row-major,
+ * 1 <= p <= 64, on the samples of the section above (1 <= d <= 64), under the triplet hinge.  For
+ * a triplet (i, j, k), a = x_i - x_j, b = x_i - z_k, u = L a, v = L b:
+ *   S = margin + |u|^2 - |v|^2,   loss = max(S, 0),   G_t = 1{S > 0} * 2 (u a^T - v b^T)
+ *
+ * tw_triplet_grad takes triplets as tw_triplet_idx32 does (absolute int32 rows, shard s owns
+ * [d_trip_off[s], d_trip_off[s + 1]), any mix of sizes, max_triplets bounds them) and writes
+ *   d_loss[s]   the shard's mean loss (an empty shard: 0)              n_shards doubles
+ *   d_active[s] #{S > 0} of the shard                                  n_shards uint64
+ *   d_G         the mean over non-empty shards of the shards' mean G_t (p, d), all zero when
+ *               every shard is empty; left untouched (and may be null) when want_grad = 0
+ * d_loss and d_active are always written.  G and the loss carry no bit contract (fused
+ * multiply-adds, sums in the kernel's order) but are run-to-run deterministic: no atomics, one
+ * partial per workgroup in d_work (tw_triplet_grad_work_bytes bytes, nothing to zero), added in
+ * workgroup order, then the shards' means in a fixed order that no schedule changes.
+ * tw_triplet_grad_tile(): triplets per workgroup.
+ *
+ * tw_triplet_project: d_out[row * p + r] = acc over c = 0 .. d-1 of acc + L[r, c] * A[row, c]
+ * from acc = 0.0, multiply and add separate — bit-exact; a NaN is written as the quiet NaN
+ * 0x7ff8000000000000.  d_a is (rows, d).
+ *
+ * tw_triplet_sgd_update, over count = p * d elements, multiply and add separate (bit-exact given
+ * d_G): g = G + reg * L; delta = lr * g (momentum = 0) or 0.9 * delta + lr * g (momentum = 1);
+ * L = L - delta.  d_L and d_delta are updated in place.
+ *
+ * Argument errors (a null pointer, d or p outside [1, 64], a negative size, want_grad or
+ * momentum not 0 / 1, a NaN margin) return TW_ERR_ARG before any launch. */
+int32_t tw_triplet_grad_tile(void);
+int64_t tw_triplet_grad_work_bytes(int32_t n_shards, int64_t max_triplets, int32_t d, int32_t p);
+int tw_triplet_grad(const double* d_x, const double* d_z, int32_t d, const double* d_L, int32_t p,
+                    const int32_t* d_i, const int32_t* d_j, const int32_t* d_k,
+                    const int64_t* d_trip_off, int32_t n_shards, int64_t max_triplets,
+                    double margin, int32_t want_grad, void* d_work, double* d_G, double* d_loss,
+                    uint64_t* d_active, void* stream);
+int tw_triplet_project(const double* d_a, int64_t rows, int32_t d, const double* d_L, int32_t p,
+                       double* d_out, void* stream);
+int tw_triplet_sgd_update(const double* d_G, double* d_L, double* d_delta, int32_t count,
+                          double reg, double lr, int32_t momentum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

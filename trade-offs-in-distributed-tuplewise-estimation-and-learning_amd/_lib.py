@@ -259,6 +259,12 @@ _SIGNATURES = {
                         _vp, _vp, _vp],
     "tw_triplet_idx_work_bytes": [_i32, _i64],
     "tw_triplet_idx32": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp],
+    "tw_triplet_grad_tile": [],
+    "tw_triplet_grad_work_bytes": [_i32, _i64, _i32, _i32],
+    "tw_triplet_grad": [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _f64, _i32, _vp,
+                        _vp, _vp, _vp, _vp],
+    "tw_triplet_project": [_vp, _i64, _i32, _vp, _i32, _vp, _vp],
+    "tw_triplet_sgd_update": [_vp, _vp, _vp, _i32, _f64, _f64, _i32, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -281,6 +287,7 @@ _RESTYPES = {
     "tw_self_sorted_work_bytes": ctypes.c_int64,
     "tw_chain_planes_work_bytes": ctypes.c_int64,
     "tw_triplet_idx_work_bytes": ctypes.c_int64,
+    "tw_triplet_grad_work_bytes": ctypes.c_int64,
 }
 
 _lib = None
