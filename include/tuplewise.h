@@ -201,21 +201,16 @@ int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off, int64_t x_
                          int32_t half, uint64_t* d_out, void* stream);
 /* tw_count_pairs_chain with the caller's promise that every x and z image is an integer in
  * [0, image_bound] (x images also: the -2^25 "never" image of a NaN score).  With the strict
- * predicate (half = 0) and image_bound < 2^24 the count runs bit-sliced (k_count_chain_bits,
- * 32 pairs per lane and instruction); half = 1 or a larger bound runs
- * tw_count_pairs_chain's packed kernel.  The counts are the same either way. */
-int tw_count_pairs_chain_bound(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
-                               const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
-                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
-                               int32_t half, int64_t image_bound, uint64_t* d_out,
-                               void* stream);
-/* tw_count_pairs_chain_bound whose bit-sliced count reads bit planes built ONCE per bag
- * (DESIGN §4.1f): a pre-pass (k_chain_planes) writes the planes of every bag's x groups (and
- * of its z groups, where the x remainder is counted with the roles swapped) into d_work, and
- * the count (k_count_chain_planes) follows on the same stream inside this call.  d_work:
- * at least tw_chain_planes_work_bytes(...) bytes (else TW_ERR_ARG before any launch), written
- * and read only inside the call — calls on different streams must not share it.  Same counts,
- * same packed-kernel cases (half = 1, a bound of 2^24 or more, tiny bags) as the _bound form. */
+ * predicate (half = 0) and image_bound < 2^24 the count runs bit-sliced (32 pairs
+ * per lane and instruction) on bit planes built ONCE per bag: a pre-pass
+ * (k_chain_planes) writes the planes of every bag's x groups (and of its z groups, where the x
+ * remainder is counted with the roles swapped) into d_work, and the count
+ * (k_count_chain_planes or its class-run form) follows on the same stream inside this call.
+ * half = 1, a bound of 2^24 or more, and bags much smaller than a plane tile (chainplan.h
+ * chain_count_sliced) run tw_count_pairs_chain's packed kernel.  The counts are the same either
+ * way.  d_work: at least tw_chain_planes_work_bytes(...) bytes (else TW_ERR_ARG before any
+ * launch), written and read only inside the call — calls on different streams must not share
+ * it. */
 int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                                 const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                                 int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
@@ -227,9 +222,9 @@ int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off, int
  * tables), sized for any plan and any class bits, so the tuning hooks do not change it. */
 int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
                                    int64_t max_nz, int32_t half, int64_t image_bound);
-/* The form of the class loop a count with nb planes and k class bits runs in this build
- * (DESIGN §4.1h, §4.1i): 3 = the digit tables, where nb - k low planes fit them; 2 = masked
- * planes and scalar loads; 0, 1 in A/B builds only.  A query: there is no hook to set it. */
+/* The form of the class loop a count with nb planes and k class bits runs (DESIGN §4.1h,
+ * §4.1i): 3 = the digit tables, where nb - k low planes fit them; 2 = masked planes and scalar
+ * loads.  A query: there is no hook to set it. */
 int32_t tw_count_chain_class_form(int32_t nb, int32_t k);
 /* A/B control of the digit loop's items: an item walks a span of `runs`
  * consecutive run-table entries of its bag and keeps what depends on its x tile alone across
@@ -997,15 +992,8 @@ int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int32_t steps, 
                           uint32_t* d_cursors, int32_t* d_flag, const int64_t* d_x_off,
                           const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
                           uint64_t* d_out, void* stream);
-/* tw_chain_unpack_count whose count is tw_count_pairs_chain_bound's (image_bound: its promise). */
-int tw_chain_unpack_count_bound(const uint64_t* d_recv, int32_t world, int32_t steps, int64_t cap,
-                                int32_t half, int64_t n_x, int64_t n_z, int64_t x_shard,
-                                int64_t z_shard, int32_t n_shards, void* d_x_bag, void* d_z_bag,
-                                uint32_t* d_cursors, int32_t* d_flag, const int64_t* d_x_off,
-                                const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
-                                int64_t image_bound, uint64_t* d_out, void* stream);
-/* tw_chain_unpack_count whose count is tw_count_pairs_chain_planes' (d_work, work_bytes: its
- * workspace, for bag strides n_x / n_z). */
+/* tw_chain_unpack_count whose count is tw_count_pairs_chain_planes' (image_bound: its promise;
+ * d_work, work_bytes: its workspace, for bag strides n_x / n_z). */
 int tw_chain_unpack_count_planes(const uint64_t* d_recv, int32_t world, int32_t steps,
                                  int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
                                  int64_t x_shard, int64_t z_shard, int32_t n_shards,

@@ -1,9 +1,9 @@
 // Host check of csrc/chainplan.h (the work items of the plane-reading chain count), no GPU:
 // tests/test_chainplan_host.py compiles and runs it.  For every plan it enumerates the items of
 // a bag and checks that their rectangles tile nx x nz exactly once, that the swap rule picks
-// the side with fewer slots, that the padded slots equal the closed form, and that the plane
-// layout is bits_transpose32's.  Prints one "ok <name>" line per check and exits non-zero at
-// the first mismatch.
+// the side with fewer slots, that the padded slots equal the closed form, that the plane
+// layout is bits_transpose32's, and pins the bit-sliced-or-packed decision.  Prints one
+// "ok <name>" line per check and exits non-zero at the first mismatch.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -165,9 +165,34 @@ static int check_layout(std::mt19937& g) {
   return 0;
 }
 
+// chain_count_sliced: which bounded launches run bit-sliced (true) and which packed
+static int check_decision() {
+  const int nb = bits_pick_nb(1000000);  // 20 planes
+  const struct {
+    int64_t max_nx;
+    bool sliced;
+  } automatic[] = {{3072, false}, {3073, true},  {4096, true},  {4097, false},  {4500, false},
+                   {6144, false}, {6145, true},  {15625, true}, {100000, true}};
+  for (const auto& c : automatic)
+    if (chain_count_sliced(c.max_nx, 0, false, nb) != c.sliced)
+      return fail("automatic decision", c.max_nx, c.sliced, nb, 0);
+  for (int R : {2, 3, 4})  // the plane plans forced: sliced however small the bag
+    if (!chain_count_sliced(1, R, false, nb)) return fail("forced planes", 1, R, nb, 0);
+  for (int R : {8, 16})  // the packed plans forced
+    if (chain_count_sliced(15625, R, false, nb)) return fail("forced packed", 15625, R, nb, 0);
+  for (int R : {0, 2, 3, 4, 8, 16}) {
+    if (chain_count_sliced(15625, R, true, nb)) return fail("half ties", 15625, R, nb, 1);
+    // no bound below 2^24: no plane count holds the images
+    if (chain_count_sliced(15625, R, false, bits_pick_nb((int64_t)1 << 24)))
+      return fail("bound 2^24", 15625, R, 0, 0);
+  }
+  std::printf("ok decision\n");
+  return 0;
+}
+
 int main() {
   std::mt19937 g(20240607u);
-  if (check_plans()) return 1;
+  if (check_plans() || check_decision()) return 1;
   if (check_layout<16>(g) || check_layout<18>(g) || check_layout<20>(g) || check_layout<22>(g) ||
       check_layout<24>(g))
     return 1;

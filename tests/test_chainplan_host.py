@@ -3,7 +3,9 @@ the host: for (nx, nz) over {0, 1, 63, 2047, 2048, 2049, 4101, 15625, 100000}^2,
 and z chunks of 8, 600 and automatic, every item of the plan is enumerated and the rectangles
 must tile nx x nz exactly once (alone and as a ragged bag of a larger launch), the swap rule
 must pick the side with fewer slots, and the padded slots must equal the closed form; the plane
-layout helpers are checked against bits_transpose32 on random images at every plane count.
+layout helpers are checked against bits_transpose32 on random images at every plane count;
+chain_count_sliced (which bounded launches run bit-sliced, which packed) is pinned at the
+thresholds of its padding rule, under every forced plan, half ties and a bound of 2^24.
 tests/native/chainplan_driver.cpp is compiled host-only and run — no GPU needed."""
 import pathlib
 import shutil
@@ -33,5 +35,6 @@ def test_chainplan_items_on_the_host(driver):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = r.stdout.split("\n")
     assert any(l.startswith("ok plans") for l in lines), r.stdout
+    assert "ok decision" in lines, r.stdout
     for nb in (16, 18, 20, 22, 24):
         assert f"ok layout NB={nb}" in lines, r.stdout

@@ -1,9 +1,11 @@
-"""The bit-sliced chain count (k_count_chain_bits) behind
-tw_count_pairs_chain_bound / tw_chain_unpack_count_bound: on bags built directly (ragged x and
-z tails, empty bags, sub-wave tiles, z bags shorter and longer than a chunk, heavy ties, the
-extreme images 0 and bound, "never" x images) its counts equal the packed kernel's
-(tw_count_pairs_chain) and a NumPy integer count, exactly, at every plane-count boundary and
-under every forced plan (R in {2, 4} plane groups, z chunks of 8 and 600)."""
+"""The bit-sliced chain count as HipOps issues it under bounded_images:
+tw_count_pairs_chain_planes / tw_chain_unpack_count_planes, that is the pre-pass k_chain_planes
+and k_count_chain_planes (launches this small run without class bits under the automatic rule),
+or the packed k_count_chain where the automatic plan keeps a launch on it.  On bags built
+directly (ragged x and z tails, empty bags, sub-wave tiles, z bags shorter and longer than a
+chunk, heavy ties, the extreme images 0 and bound, "never" x images) its counts equal the packed
+kernel's (tw_count_pairs_chain) and a NumPy integer count, exactly, at every plane-count
+boundary and under every forced plan (R in {2, 4} plane groups, z chunks of 8 and 600)."""
 import numpy as np
 import pytest
 
@@ -92,8 +94,9 @@ def test_bound_count_equals_packed_and_numpy(gpu, bound):
 @pytest.mark.parametrize("plan", [(0, 0), (2, 8), (4, 600)])
 def test_unpack_count_bound_equals_unpack_count(gpu, plan):
     """One world-1 receive buffer (tw_chain_emit's exchange layout: per step a count slot, then
-    {image | local position << 32} records): tw_chain_unpack_count_bound == tw_chain_unpack_count
-    == NumPy on the prop-SWOR shard regions."""
+    {image | local position << 32} records): HipOps.chain_unpack_count under bounded_images
+    (tw_chain_unpack_count_planes) == tw_chain_unpack_count == NumPy on the prop-SWOR shard
+    regions."""
     import torch
     from tuplewise import _lib as L
     from tuplewise.device import HipOps, prop_swor_layout

@@ -3,9 +3,8 @@ DESIGN §4.1f) behind tw_count_pairs_chain_planes / tw_chain_unpack_count_planes
 one launch (empty, sub-wave, one image short of a plane group, exactly one, one more, several
 groups with a remainder, the bench's 15625; z bags shorter and longer than a group and a chunk)
 with heavy ties, the extreme images 0 and bound, "never" x images — counts equal, exactly, a
-NumPy integer count, the packed kernel (tw_count_pairs_chain) and the old bit-sliced entry
-(tw_count_pairs_chain_bound, called directly), at every plane-count boundary and under the
-forced plans (2, 8), (3, 600), (4, 600) and the automatic one.  The workspace holds 0xFF before
+NumPy integer count and the packed kernel (tw_count_pairs_chain), at every plane-count boundary
+and under the forced plans (2, 8), (3, 600), (4, 600) and the automatic one.  The workspace holds 0xFF before
 every call: a plane word read without having been written would count every pair."""
 import numpy as np
 import pytest
@@ -61,7 +60,7 @@ def _bags(seed, bound):
 
 
 class _Launch:
-    """One set of bags on the device and the three entry points on them."""
+    """One set of bags on the device and the two entry points on them."""
 
     def __init__(self, torch, L, bound, seed):
         self.torch, self.L, self.bound = torch, L, bound
@@ -86,12 +85,6 @@ class _Launch:
                     self.L.stream_handle())
         return o
 
-    def old_bits(self):
-        o = self.out()
-        self.L.call("tw_count_pairs_chain_bound", *self.head, self.bound, o,
-                    self.L.stream_handle())
-        return o
-
     def planes(self, work, work_bytes=None):
         o = self.out()
         self.L.call("tw_count_pairs_chain_planes", *self.head, self.bound, o,
@@ -101,7 +94,7 @@ class _Launch:
 
 
 @pytest.mark.parametrize("bound", BOUNDS)
-def test_planes_count_equals_numpy_packed_and_old_bits(gpu, bound):
+def test_planes_count_equals_numpy_and_packed(gpu, bound):
     import torch
     from tuplewise import _lib as L
     assert float(np.float32(bound)) == bound  # the images are exact in f32
@@ -115,10 +108,6 @@ def test_planes_count_equals_numpy_packed_and_old_bits(gpu, bound):
     try:
         for R, zc in PLANS:
             L.call("tw_count_chain_set_plan", R, zc)
-            old = a.old_bits().cpu().numpy()
-            print("bound", bound, "plan", (R, zc), "max |old bits - numpy|",
-                  np.abs(old - a.want).max())
-            assert np.array_equal(old, a.want), (R, zc)
             # the x remainders swapped wherever the per-bag rule allows (2), never (0), and as
             # the automatic plan decides for a launch this small (1)
             for swap in (2, 0, 1):
@@ -184,8 +173,7 @@ def test_undersized_workspace_is_refused_before_any_launch(gpu):
 def test_unpack_count_planes_equals_unpack_count(gpu, plan):
     """One world-1 receive buffer (tw_chain_emit's exchange layout: per step a count slot, then
     {image | local position << 32} records): tw_chain_unpack_count_planes ==
-    tw_chain_unpack_count_bound == tw_chain_unpack_count == NumPy on the prop-SWOR shard
-    regions (shards of 4500 x and 2500 z: two full groups and a swapped remainder)."""
+    tw_chain_unpack_count == NumPy on the prop-SWOR shard regions (shards of 4500 x and 2500 z: two full groups and a swapped remainder)."""
     import torch
     from tuplewise import _lib as L
     from tuplewise.device import HipOps, prop_swor_layout
@@ -228,7 +216,6 @@ def test_unpack_count_planes_equals_unpack_count(gpu, plan):
     try:
         L.call("tw_count_chain_set_plan", *plan)
         L.call("tw_count_chain_set_swap", 2)
-        old = run("tw_chain_unpack_count_bound", bound, ..., None)
         work.fill_(0xFF)
         got = run("tw_chain_unpack_count_planes", bound, ..., None, work, wb)
         if plan != (0, 0):  # (the automatic plan keeps bags this small on the packed kernel)
@@ -246,7 +233,6 @@ def test_unpack_count_planes_equals_unpack_count(gpu, plan):
         L.call("tw_count_chain_set_plan", 0, 0)
         L.call("tw_count_chain_set_swap", 1)
     print("plan", plan, "max |planes - numpy|", np.abs(got - want).max())
-    assert np.array_equal(old, want)
     assert np.array_equal(got, want)
     assert np.array_equal(routed, want)
     with pytest.raises(ValueError, match="work_bytes"):

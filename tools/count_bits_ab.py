@@ -1,9 +1,9 @@
 """In-process A/B of the chain count's two kernels (csrc/chain.hip) on tools/count_plan_ab.py's
 shapes: tw_count_pairs_chain (packed f32, k_count_chain) against the bounded count HipOps
-issues (bit-sliced where plan_chain lets it: since DESIGN §4.1f tw_count_pairs_chain_planes,
-k_chain_planes + k_count_chain_planes; tools/count_planes_ab.py compares that with the older
-k_count_chain_bits) under the automatic plan, and forced to R = 2 and R = 4 plane groups.  Interleaved over 7 rounds; per
-variant the median, min and max ms; counts must agree exactly.  The automatic rule is right
+issues (tw_count_pairs_chain_planes: bit-sliced on planes built once per bag, k_chain_planes +
+k_count_chain_planes or its class-run form, where chainplan.h's chain_count_sliced lets it)
+under the automatic plan, and forced to R = 2 and R = 4 plane groups.  Interleaved over 7
+rounds; per variant the median, min and max ms; counts must agree exactly.  The automatic rule is right
 where "bound" is no slower than "packed" beyond the packed rounds' own spread.
 Run on the GPU box:  python tools/count_bits_ab.py [out.json]"""
 import json

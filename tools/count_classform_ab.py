@@ -1,26 +1,18 @@
-"""A/B of the class loop's build-time forms (csrc/chainclass.h TW_CLASS_FORM / TW_CLASS_BATCH /
-TW_CLASS_DIGIT_R) on tools/count_classes_ab.py's shapes.  One fresh child
-process per variant library (`make -C <pkg>/csrc ab-classform` -> tools/variants/libtuplewise_classform*.so, chosen
-with TW_LIB_PATH; "product" is the library as built), the children alternated over REPS passes.
-Inside each child, tw_count_pairs_chain_planes with classes off (tw_count_chain_set_class_bits
-0: k_count_chain_planes, which no form touches — the in-process yardstick), under the automatic
-rule, and under automatic class bits with the x remainder never swapped
-(tw_count_chain_set_swap 0) and swapped wherever chainplan.h's per-bag rule allows (2),
-interleaved over 7 rounds; per setting the median, min and max ms of the whole native call
-(both pre-passes + count) and the ratio of medians to k = 0 of the same process.  Counts must
-agree exactly.
-Run on the GPU box:  python tools/count_classform_ab.py [out.json [variant ...]]
-(variants by file suffix, e.g. classform1 classform2b16 classform3r2 — form 3, the digit
-tables, with R groups per item; default: every library present)
+"""Sweeps of the class count's run-time hooks on tools/count_classes_ab.py's shapes, with the
+library as built (the class loop's build-time forms this tool once compared are retired: DESIGN
+§4.1h, §4.1i).  One fresh child process per pass, REPS passes; inside each child
+tw_count_pairs_chain_planes under every setting of the sweep, interleaved over 7 rounds; per
+setting the median, min and max ms of the whole native call (both pre-passes + count) and the
+ratio of medians to the sweep's base setting in the same process.  Counts must agree exactly.
+Run on the GPU box:  python tools/count_classform_ab.py --spans|--digits [out.json]
 
---spans [out.json]: the span sweep of DESIGN §4.1j on the same shapes with the product library:
-under the automatic class bits and swap rule, tw_count_chain_class_span forced to 1, 2, 4, 8,
-16, 32 and the whole bag, and the automatic rule, interleaved over the rounds; per shape and
+--spans [out.json]: the span sweep of DESIGN §4.1j: under the automatic class bits and swap
+rule, tw_count_chain_class_span forced to 1, 2, 4, 8, 16, 32 and the whole bag, and the automatic rule, interleaved over the rounds; per shape and
 span the median, min and max ms, the ratio of medians to M = 1 of the same process, and M = 1's
 own spread (max - min) / median, against which a shape's automatic setting is judged.
 
---digits [out.json]: the digit-width sweep of DESIGN §4.1k, same shapes, product library, one
-process per pass: under the automatic class bits, swap rule and span, tw_count_chain_class_digits
+--digits [out.json]: the digit-width sweep of DESIGN §4.1k, same shapes, one process per
+pass: under the automatic class bits, swap rule and span, tw_count_chain_class_digits
 forced to 3 (the four-digit loop), to 4 (the wide digits where NB - K = 12) and automatic,
 interleaved over the rounds; per shape the ratio of medians of the whole native call to the
 four-digit loop and the four-digit loop's own spread.  Shapes whose automatic class bits leave a
@@ -32,11 +24,8 @@ import subprocess
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-VARIANTS = ROOT / "tools" / "variants"
 ROUNDS, REPS = 7, 2
 # (name, class bits, swap, span): span 0 is the automatic rule
-SETTINGS = [("k=0", 0, 1, 0), ("automatic", -1, 1, 0), ("automatic, swap 0", -1, 0, 0),
-            ("automatic, swap 2", -1, 2, 0)]
 WHOLE_BAG = 1 << 20  # (clamped to the launch's table capacity)
 SPAN_SETTINGS = [("M=1", -1, 1, 1)] + [(f"M={m}", -1, 1, m) for m in (2, 4, 8, 16, 32)] + [
     ("M=whole bag", -1, 1, WHOLE_BAG), ("automatic", -1, 1, 0)]
@@ -49,7 +38,7 @@ SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1
           ("G=8 K=20", 8, 20), ("C2", 0, 1), ("remainder 100 K=20", -1, 20)]
 
 
-def child(settings=SETTINGS, base="k=0"):
+def child(settings, base):
     sys.path.insert(0, str(ROOT))
     import numpy as np
     import torch
@@ -139,41 +128,8 @@ def spans_main(flag="--spans-child", settings=SPAN_SETTINGS, base="M=1",
                                                     indent=1) + "\n")
 
 
-def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else None
-    libs = {"product": None}
-    for p in sorted(VARIANTS.glob("libtuplewise_classform*.so")):
-        libs[p.stem.replace("libtuplewise_", "")] = p
-    if len(sys.argv) > 2:
-        libs = {k: v for k, v in libs.items() if k in sys.argv[2:]}
-    passes = {k: [] for k in libs}
-    for rep in range(REPS):
-        for k, lib in libs.items():
-            env = dict(os.environ)
-            env.pop("TW_LIB_PATH", None)
-            if lib is not None:
-                env["TW_LIB_PATH"] = str(lib)
-            r = subprocess.run([sys.executable, __file__, "--child"], env=env,
-                               capture_output=True, text=True, timeout=600)
-            if r.returncode != 0:
-                print(k, "failed:", r.stderr[-1500:], flush=True)
-                sys.exit(1)
-            rows = json.loads(r.stdout.strip().splitlines()[-1])
-            passes[k].append(rows)
-            print(f"pass {rep} {k}: " + "  ".join(
-                f"{row['shape']} " + "/".join(f"{row['ratio to k=0'][s[0]]:.4f}"
-                                              for s in SETTINGS[1:]) for row in rows), flush=True)
-            if out:
-                pathlib.Path(out).write_text(json.dumps(
-                    {"what": "ratio of medians to k = 0 inside each child (automatic / swap 0 / "
-                             "swap 2 printed); one child per library and pass",
-                     "passes": passes}, indent=1) + "\n")
-
-
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["--child"]:
-        child()
-    elif sys.argv[1:2] == ["--spans-child"]:
+    if sys.argv[1:2] == ["--spans-child"]:
         child(SPAN_SETTINGS, "M=1")
     elif sys.argv[1:2] == ["--spans"]:
         spans_main()
@@ -186,4 +142,4 @@ if __name__ == "__main__":
                    "call and the ratio of medians to the four-digit loop inside each child; one "
                    "child per pass")
     else:
-        main()
+        sys.exit(__doc__)

@@ -17,15 +17,13 @@ PAIRS_PER_STEP = 64 * 15625 * 15625  # n = 1e6/class, N = 64 shards
 PEAK = 256 * 64 * 2.4e9  # lane-op/s
 
 path, K, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
-# (the strict count: the packed k_count_chain<R, false>, the bit-sliced k_count_chain_bits<NB, R>,
-# the plane-reading k_count_chain_planes<NB>, whose launch's time includes its pre-pass
-# k_chain_planes<NB>, the launch just before it on the stream, or its class-run form
-# k_count_chain_classes<NB, K>, whose time includes both pre-passes: k_chain_planes<NB> and
-# k_chain_zclasses)
+# (the strict count: the packed k_count_chain<R, false>, the plane-reading
+# k_count_chain_planes<NB>, whose launch's time includes its pre-pass k_chain_planes<NB>, the
+# launch just before it on the stream, or its class-run form k_count_chain_classes<NB, K>, whose
+# time includes both pre-passes: k_chain_planes<NB> and k_chain_zclasses)
 every = list(csv.DictReader(open(path)))
 rows = [r for r in every
         if ("k_count_chain<" in r["Kernel_Name"] and ", false>" in r["Kernel_Name"])
-        or "k_count_chain_bits<" in r["Kernel_Name"]
         or "k_count_chain_planes<" in r["Kernel_Name"]
         or "k_count_chain_classes<" in r["Kernel_Name"]]
 pre = sorted((r for r in every if "k_chain_planes<" in r["Kernel_Name"]),

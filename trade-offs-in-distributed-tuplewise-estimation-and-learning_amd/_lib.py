@@ -56,8 +56,6 @@ _SIGNATURES = {
                         _vp],
     "tw_count_pairs_chain": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32, _vp,
                              _vp],
-    "tw_count_pairs_chain_bound": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32,
-                                   _i64, _vp, _vp],
     "tw_count_pairs_chain_planes": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32,
                                     _i64, _vp, _vp, _vp, _i64],
     "tw_chain_planes_work_bytes": [_i32, _i32, _i64, _i64, _i32, _i64],
@@ -213,8 +211,6 @@ _SIGNATURES = {
     "tw_chain_final_scatter": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "tw_chain_unpack_count": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp,
                               _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
-    "tw_chain_unpack_count_bound": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32,
-                                    _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
     "tw_chain_unpack_count_planes": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
                                      _vp, _i64],

@@ -1,5 +1,6 @@
 // bitcount.h — the bit-sliced compare-and-count of rank images (csrc/chain.hip's
-// k_count_chain_bits), beside pkcount.h's packed-f32 form.
+// k_count_chain_planes and its class-run forms), beside pkcount.h's packed-f32
+// form.
 //
 // Images are integers in [0, bound], bound < 2^NB <= 2^24.  A lane keeps 32 x images as NB bit
 // PLANES (plane b: bit k = bit b of image k), and the unsigned compare x > z is the carry out of
@@ -139,60 +140,11 @@ __device__ __forceinline__ void bits_scalar_loop(const uint32_t (&pl)[R][NB], ui
   }
 }
 
-// One wave item: 64 * 32 * R x images [x0, min(x0 + 64 * 32 * R, xe)) of a bag (R plane groups
-// per lane; group r, bit k of a lane is image x0 + (32 r + k) * 64 + lane; slots past xe hold 0)
-// against its z images [z0, z1).  z goes 64 at a time through one VGPR (coalesced load,
-// converted on the VALU, the next 64 in flight) and reaches the scalar side by v_readlane_b32:
-// one extra VALU instruction per z and wave.  Returns the lane's count (sum over the wave =
-// the item's pairs).
-template <int NB, int R>
-__device__ __forceinline__ unsigned long long bits_count_item(const float* __restrict__ xf,
-                                                              int64_t x0, int64_t xe,
-                                                              const float* __restrict__ zf,
-                                                              int64_t z0, int64_t z1, int lane) {
-  uint32_t pl[R][NB], acc[R];
-  const float* __restrict__ xp = xf + bits_uniform(x0);
-  const int nx =  // >= 1
-      __builtin_amdgcn_readfirstlane((int)min((int64_t)(64 * 32 * R), xe - x0));
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    float raw[32];
-    uint32_t a[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k)  // all of a group's loads in flight together ...
-      raw[k] = xp[min((r * 32 + k) * 64 + lane, nx - 1)];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-      asm volatile("" : "+v"(raw[k]));  // ... and none sunk behind a branch on the select below
-      a[k] = (r * 32 + k) * 64 + lane < nx ? bits_x_image(raw[k]) : 0u;
-    }
-    bits_transpose32(a);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      pl[r][b] = a[b];
-      asm volatile("" : "+v"(pl[r][b]));  // the planes made here: one group's 32 + 32
-    }                                      // temporaries at a time, not every group's
-    acc[r] = 0;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  const int nz = __builtin_amdgcn_readfirstlane((int)(z1 - z0));
-  const float* __restrict__ zp = zf + bits_uniform(z0);
-  auto z_load = [&](int j) -> uint32_t {
-    const uint32_t v = bits_z_image(zp[min(j + lane, nz - 1)]);  // (no branch around the load)
-    return j + lane < nz ? v : kBitsZNever;
-  };
-  bits_scalar_loop<NB, R>(pl, acc, nz, z_load);
-  unsigned long long tot = 0;
-#pragma unroll
-  for (int r = 0; r < R; ++r) tot += acc[r];
-  return tot;
-}
-
 // One wave item on planes built beforehand (chainplan.h; chain.hip's k_chain_planes): R groups
 // of NB plane words per lane at pw (group r, plane b: pw[(r * NB + b) * 64 + lane]) against
 // the ns scalar-side images at sf — a z chunk (stored negated; complemented here), or, with
 // the roles SWAPPED, x images against complemented z planes: the carry out of x + ~z does not
-// care which operand is the lane's.  The scalar loop is bits_count_item's; padded scalar
+// care which operand is the lane's.  The scalar loop is bits_scalar_loop; padded scalar
 // slots hold 0 in either role (a complemented z that is never less, an x that is never more).
 template <int NB, int R>
 __device__ __forceinline__ unsigned long long bits_count_planes(const uint32_t* __restrict__ pw,

@@ -528,34 +528,9 @@ __global__ __launch_bounds__(kBlock) void k_count_chain(
       });
 }
 
-// The bit-sliced count (bitcount.h; strict predicate, images in [0, 2^NB)): an item is
-// 64 * 32 * R x images as R groups of NB bit planes per lane against one z chunk, NB + 1 VALU
-// instructions per 64 * 32 pairs where the packed form takes 32.  Same work items, XCD order,
-// ragged tails (x slots past the bag hold image 0, z slots past the chunk the complemented 0)
-// and epilogue as k_count_chain.
-template <int NB, int R>
-__device__ __forceinline__ unsigned long long count_chain_item_bits(
-    const float* __restrict__ xf, int64_t x0, int64_t xe, const float* __restrict__ zf,
-    int64_t z0, int64_t z1, int lane) {
-  return wave_sum_u64(bits_count_item<NB, R>(xf, x0, xe, zf, z0, z1, lane));
-}
-
-template <int NB, int R>
-__global__ __launch_bounds__(kBlock) void k_count_chain_bits(
-    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
-    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
-    int n_shards, int n_bags, int tiles_x, int zchunks, int64_t z_chunk,
-    unsigned long long* __restrict__ out) {
-  count_chain_block<kWave * 32 * R>(
-      x_off, x_stride, z_off, z_stride, n_shards, n_bags, tiles_x, zchunks, z_chunk, out,
-      [&](int64_t x0, int64_t xe, int64_t z0, int64_t z1, int lane) {
-        return count_chain_item_bits<NB, R>(xb, x0, xe, zb, z0, z1, lane);
-      });
-}
-
-// The bit-sliced count on planes built once per bag (chainplan.h).
-// k_count_chain_bits transposes an x tile in every one of the bag's z chunks (16 times at the
-// bench shape) and pads the x tail to a whole group.  Here a pre-pass makes the planes once:
+// The bit-sliced count (bitcount.h; strict predicate, images in [0, 2^NB)) on planes built once
+// per bag (chainplan.h): NB + 1 VALU instructions per 64 * 32 pairs where the
+// packed form takes 32.  A pre-pass makes the planes once:
 // one wave per (bag, group of 2048 images, side) loads the group's 32 images per lane (bit k
 // of lane l: image g * 2048 + k * 64 + l), converts them (x: bits_x_image; z: complemented,
 // bits_z_image), transposes and stores NB planes of 64 u32 — one 256-B store each.  Slots past
@@ -776,20 +751,14 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
       const uint32_t* __restrict__ zbag =
           work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride);
       unsigned long long t;
-#if TW_CLASS_FORM == 3
-#if TW_CLASS_WIDE
       if constexpr (DW == kClassWideBits) {  // the wide-digit loop: NB - K = 12, R <= 2
-        static_assert(class_wide_built(NB, K), "the wide digits take the 12-plane low field");
+        static_assert(class_wide_fit(NB - K), "the wide digits take the 12-plane low field");
         t = bits_count_span_wide_of<NB, K, kClassDigitsMaxR>(pw, zbag, tab, sp.e1 - sp.e0, lane,
                                                              ng);
-      } else
-#endif
-      if constexpr (class_loop_form(NB, K) == 3) {  // the digit loop: the launcher planned
+      } else if constexpr (class_loop_form(NB, K) == 3) {  // the digit loop: the launcher planned
         t = bits_count_span_digits_of<NB, K, kClassDigitsMaxR>(  // R <= kClassDigitsMaxR
             pw, zbag, tab, sp.e1 - sp.e0, lane, ng);
-      } else
-#endif
-      {  // the masked-plane loop: one run per item (the launcher planned cp.span = 1)
+      } else {  // the masked-plane loop: one run per item (the launcher planned cp.span = 1)
         const ClassRun r = class_entry((uint32_t)__builtin_amdgcn_readfirstlane((int)tab[0]),
                                        (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[1]));
         const uint32_t* __restrict__ zs = zbag + r.z0;
@@ -985,10 +954,9 @@ __global__ __launch_bounds__(kBlock) void k_chain_scatter(const uint64_t* __rest
 }
 
 // ----------------------------------------------------------------------------- plan
-struct ChainPlan {
+struct ChainPlan {  // of the packed kernel
   int R, tiles_x, zchunks;
   int64_t z_chunk, blocks;
-  int nb;  // bit planes of k_count_chain_bits; 0: the packed kernel
 };
 static int g_chain_R = 0;  // tuning hooks (tw_count_chain_set_plan); 0 = automatic
 static int64_t g_chain_zchunk = 0;
@@ -1008,27 +976,10 @@ constexpr int64_t kChainItems = 256 * 4 * 150;
 // (C2's single 1e5 x 1e5 bag: 600-image chunks 276.9 us, 512 282.3 us, profiles/
 // r05s59_c2_plan.log; the large shapes are indifferent between 512 and 1024)
 constexpr int64_t kChainMinZ = 600;
-// The bit-sliced kernel (nb > 0: strict predicate and an image bound below 2^24 given): R in
-// {2, 4} plane groups per lane, x tiles of 64 * 32 * R images, least padded slots; on a tie
-// R = 4, or R = 2 where 4 would leave fewer than ~2 items per SIMD (a G = 8 rank's K = 4
-// chunk, 32 bags: 0.190 against 0.206 ms).  An item opens with its bit transposes (~780 VALU
-// instructions per group against R * (nb + 1) + 1 per z), so chunks are longer than the
-// packed kernel's: >= kBitsMinZ images, as many as give ~40 items per SIMD (kBitsItems), of
-// even length.  A bag much smaller than a tile pads more slots than the bit-sliced loop
-// gains (1.39x per slot, profiles/r07_mb_bits.log): past kBitsMaxPad x the packed plan's
-// slots the packed kernel keeps the launch.  tools/count_bits_ab.py, interleaved A/B against
-// the packed kernel (profiles/r07_count_bits_ab.json): headline K = 20 8.48 -> 5.77 ms,
-// K = 32 13.26 -> 9.07, K = 4 1.79 -> 1.19; per-rank shapes G = 2 / 4 / 8 at K = 20 0.66-0.67
-// of the packed time, C2 (one 1e5 x 1e5 bag, R = 2) 0.294 -> 0.260; none slower.
-// (The _planes entries keep this function's choice between the packed and the bit-sliced
-// count — kBitsMaxPad included — and then plan their own items: chainplan.h's planes_plan,
-// whose items have no transposes to amortise and are much shorter.)
-constexpr int64_t kBitsItems = 256 * 4 * 40;
-constexpr int64_t kBitsMinZ = 1024;
-constexpr double kBitsMaxPad = 1.25;
-static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool half,
-                            int nb) {
-  ChainPlan p{half ? 8 : 16, 1, 1, max_nz, 0, 0};
+// (Whether a bounded launch runs this kernel or the bit-sliced count: chainplan.h's
+// chain_count_sliced.)
+static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool half) {
+  ChainPlan p{half ? 8 : 16, 1, 1, max_nz, 0};
   int64_t best = -1;
   if (!half) {
     for (int R : {16, 8}) {
@@ -1039,42 +990,17 @@ static ChainPlan plan_chain(int64_t max_nx, int64_t max_nz, int64_t n_bags, bool
         p.R = R;
       }
     }
-    if (nb > 0 && g_chain_R != 8 && g_chain_R != 16) {
-      int64_t bbest = -1;
-      int bR = 0;
-      // on a tie R = 4, unless that leaves fewer than ~2 items per SIMD (R = 2: twice as many)
-      const bool few = ceil_div(max_nx, (int64_t)kWave * 32 * 4) * n_bags *
-                           ceil_div(max_nz, kBitsMinZ) < 256 * 4 * 2;
-      const int tieR = few ? 2 : 4;
-      const int forceR = g_chain_R == 3 ? 4 : g_chain_R;  // (3: k_count_chain_planes only)
-      for (int R : {tieR, 6 - tieR}) {
-        if (forceR && R != forceR) continue;
-        const int64_t slots = ceil_div(max_nx, (int64_t)kWave * 32 * R) * kWave * 32 * R;
-        if (bbest < 0 || slots < bbest) {
-          bbest = slots;
-          bR = R;
-        }
-      }
-      if (g_chain_R || (double)bbest <= kBitsMaxPad * (double)best) {
-        p.R = bR;
-        p.nb = nb;
-      }
-    }
   }
-  const int64_t tile = p.nb ? (int64_t)kWave * 32 * p.R : (int64_t)kWave * p.R;
-  p.tiles_x = (int)ceil_div(max_nx, tile);
+  p.tiles_x = (int)ceil_div(max_nx, (int64_t)kWave * p.R);
   const int64_t base = (int64_t)p.tiles_x * n_bags;
   int64_t zc = g_chain_zchunk;
   if (zc <= 0)
     zc = std::max<int64_t>(
-        p.nb ? kBitsMinZ : kChainMinZ,
-        ceil_div(max_nz, std::max<int64_t>(1, ceil_div(p.nb ? kBitsItems : kChainItems,
-                                                       std::max<int64_t>(1, base)))));
+        kChainMinZ, ceil_div(max_nz, std::max<int64_t>(1, ceil_div(kChainItems,
+                                                                   std::max<int64_t>(1, base)))));
   zc = std::min<int64_t>(zc, (int64_t)1 << 24);  // f32 lane counters stay exact
   p.z_chunk = ceil_div(std::min<int64_t>(zc, max_nz), 8) * 8;
   p.zchunks = (int)ceil_div(max_nz, p.z_chunk);
-  if (p.nb && g_chain_zchunk <= 0)  // the same number of chunks, of even length
-    p.z_chunk = ceil_div(ceil_div(max_nz, (int64_t)p.zchunks), 8) * 8;
   p.blocks = ceil_div((int64_t)p.tiles_x * p.zchunks * n_bags, kBlock / kWave);
   return p;
 }
@@ -1329,8 +1255,7 @@ namespace tw {
 static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                               const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
-                              int32_t half, int64_t image_bound, uint64_t* d_out,
-                              hipStream_t st);
+                              int32_t half, uint64_t* d_out, hipStream_t st);
 // ... and of the _planes entries (d_work: their plane workspace)
 static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                                    const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
@@ -1339,11 +1264,11 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
                                    uint64_t* d_out, void* d_work, hipStream_t st);
 }  // namespace tw
 
-static int count_pairs_chain_impl(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
-                                  const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
-                                  int32_t n_shards, int32_t steps, int64_t max_nx,
-                                  int64_t max_nz, int32_t half, int64_t image_bound,
-                                  uint64_t* d_out, void* stream) {
+extern "C" int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off,
+                                    int64_t x_stride, const void* d_z_bag,
+                                    const int64_t* d_z_off, int64_t z_stride, int32_t n_shards,
+                                    int32_t steps, int64_t max_nx, int64_t max_nz, int32_t half,
+                                    uint64_t* d_out, void* stream) {
   TW_ARG_CHECK(n_shards >= 0 && steps >= 0 && max_nx >= 0 && max_nz >= 0 && x_stride >= 0 &&
                    z_stride >= 0 && (half == 0 || half == 1),
                "tw_count_pairs_chain: bad sizes");
@@ -1353,32 +1278,7 @@ static int count_pairs_chain_impl(const void* d_x_bag, const int64_t* d_x_off, i
   if (bags == 0) return TW_OK;
   TW_HIP_CHECK(tw_zero_async(d_out, 0, sizeof(uint64_t) * (size_t)bags, st));
   return count_chain_launch(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride, n_shards,
-                            steps, max_nx, max_nz, half, image_bound, d_out, st);
-}
-
-extern "C" int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off,
-                                    int64_t x_stride, const void* d_z_bag,
-                                    const int64_t* d_z_off, int64_t z_stride, int32_t n_shards,
-                                    int32_t steps, int64_t max_nx, int64_t max_nz, int32_t half,
-                                    uint64_t* d_out, void* stream) {
-  return count_pairs_chain_impl(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride,
-                                n_shards, steps, max_nx, max_nz, half, -1, d_out, stream);
-}
-
-// tw_count_pairs_chain with the caller's promise that every x and z image lies in
-// [0, image_bound] (x also: the -2^25 "never" image): the strict predicate with
-// image_bound < 2^24 takes the bit-sliced kernel (k_count_chain_bits), everything else the
-// packed one.  Same counts either way.
-extern "C" int tw_count_pairs_chain_bound(const void* d_x_bag, const int64_t* d_x_off,
-                                          int64_t x_stride, const void* d_z_bag,
-                                          const int64_t* d_z_off, int64_t z_stride,
-                                          int32_t n_shards, int32_t steps, int64_t max_nx,
-                                          int64_t max_nz, int32_t half, int64_t image_bound,
-                                          uint64_t* d_out, void* stream) {
-  TW_ARG_CHECK(image_bound >= 0, "tw_count_pairs_chain_bound: image_bound >= 0");
-  return count_pairs_chain_impl(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride,
-                                n_shards, steps, max_nx, max_nz, half, image_bound, d_out,
-                                stream);
+                            steps, max_nx, max_nz, half, d_out, st);
 }
 
 // Over ranks, a chunk's receive side in ONE call: the unpack's cursors and the counts zeroed by
@@ -1405,7 +1305,7 @@ static int chain_unpack_count_impl(const uint64_t* d_recv, int32_t world, int32_
                                      int32_t* d_flag, const int64_t* d_x_off,
                                      const int64_t* d_z_off, int64_t max_nx, int64_t max_nz,
                                      int64_t image_bound, uint64_t* d_out, void* stream,
-                                     void* d_work = nullptr) {
+                                     void* d_work = nullptr) {  // (image_bound: with d_work)
   TW_ARG_CHECK(world >= 1 && steps >= 0 && steps <= kChainMax && cap >= 1 && n_x >= 0 &&
                    n_z >= 0 && (half == 0 || half == 1) && (int64_t)world * steps < 65536 &&
                    x_shard >= 0 && z_shard >= 0 && n_shards >= 0 && n_shards < kEmMaxBig &&
@@ -1434,7 +1334,7 @@ static int chain_unpack_count_impl(const uint64_t* d_recv, int32_t world, int32_
     return count_chain_launch_work(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
                                    max_nx, max_nz, half, image_bound, d_out, d_work, st);
   return count_chain_launch(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
-                            max_nx, max_nz, half, image_bound, d_out, st);
+                            max_nx, max_nz, half, d_out, st);
 }
 
 extern "C" int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int32_t steps,
@@ -1449,67 +1349,21 @@ extern "C" int tw_chain_unpack_count(const uint64_t* d_recv, int32_t world, int3
                                  max_nx, max_nz, -1, d_out, stream);
 }
 
-// tw_chain_unpack_count with tw_count_pairs_chain_bound's promise for the count
-extern "C" int tw_chain_unpack_count_bound(const uint64_t* d_recv, int32_t world, int32_t steps,
-                                           int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
-                                           int64_t x_shard, int64_t z_shard, int32_t n_shards,
-                                           void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
-                                           int32_t* d_flag, const int64_t* d_x_off,
-                                           const int64_t* d_z_off, int64_t max_nx,
-                                           int64_t max_nz, int64_t image_bound, uint64_t* d_out,
-                                           void* stream) {
-  TW_ARG_CHECK(image_bound >= 0, "tw_chain_unpack_count_bound: image_bound >= 0");
-  return chain_unpack_count_impl(d_recv, world, steps, cap, half, n_x, n_z, x_shard, z_shard,
-                                 n_shards, d_x_bag, d_z_bag, d_cursors, d_flag, d_x_off, d_z_off,
-                                 max_nx, max_nz, image_bound, d_out, stream);
-}
-
 namespace tw {
-template <int NB>
-static void count_chain_launch_bits(const ChainPlan& p, const float* xb, const int64_t* d_x_off,
-                                    int64_t x_stride, const float* zb, const int64_t* d_z_off,
-                                    int64_t z_stride, int n_shards, int bags,
-                                    unsigned long long* o, hipStream_t st) {
-  dim3 g((unsigned)p.blocks), b(kBlock);
-  if (p.R == 4)
-    hipLaunchKernelGGL((k_count_chain_bits<NB, 4>), g, b, 0, st, xb, d_x_off, x_stride, zb,
-                       d_z_off, z_stride, n_shards, bags, p.tiles_x, p.zchunks, p.z_chunk, o);
-  else
-    hipLaunchKernelGGL((k_count_chain_bits<NB, 2>), g, b, 0, st, xb, d_x_off, x_stride, zb,
-                       d_z_off, z_stride, n_shards, bags, p.tiles_x, p.zchunks, p.z_chunk, o);
-}
-
-// image_bound < 0: no bound promised (the packed kernel)
+// the packed kernel
 static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                               const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                               int32_t n_shards, int32_t steps, int64_t max_nx, int64_t max_nz,
-                              int32_t half, int64_t image_bound, uint64_t* d_out,
-                              hipStream_t st) {
+                              int32_t half, uint64_t* d_out, hipStream_t st) {
   const int64_t bags = (int64_t)n_shards * steps;
   if (max_nx == 0 || max_nz == 0) return TW_OK;
-  const ChainPlan p = plan_chain(max_nx, max_nz, bags, half != 0, bits_pick_nb(image_bound));
+  const ChainPlan p = plan_chain(max_nx, max_nz, bags, half != 0);
   TW_ARG_CHECK(p.blocks * (kBlock / kWave) < (1ll << 31) && bags < (1ll << 31),
                "tw_count_pairs_chain: grid too large");
   dim3 g((unsigned)p.blocks), b(kBlock);
   auto* o = (unsigned long long*)d_out;
   const float* zb = (const float*)d_z_bag;
-  const float* xf = (const float*)d_x_bag;
-  if (p.nb == 16)
-    count_chain_launch_bits<16>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
-                                (int)bags, o, st);
-  else if (p.nb == 18)
-    count_chain_launch_bits<18>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
-                                (int)bags, o, st);
-  else if (p.nb == 20)
-    count_chain_launch_bits<20>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
-                                (int)bags, o, st);
-  else if (p.nb == 22)
-    count_chain_launch_bits<22>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
-                                (int)bags, o, st);
-  else if (p.nb == 24)
-    count_chain_launch_bits<24>(p, xf, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards,
-                                (int)bags, o, st);
-  else if (half)
+  if (half)
     hipLaunchKernelGGL((k_count_chain<8, true>), g, b, 0, st, d_x_bag, d_x_off, x_stride, zb,
                        d_z_off, z_stride, n_shards, (int)bags, p.tiles_x, p.zchunks, p.z_chunk,
                        o);
@@ -1552,7 +1406,7 @@ static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, 
         b(kBlock);
 #define TW_CLASS_CASE(K)                                                                       \
   case K:                                                                                      \
-    if constexpr (class_wide_built(NB, K)) {                                                   \
+    if constexpr (class_wide_fit(NB - K)) {                                                    \
       if (cp.dbits == kClassWideBits) {                                                        \
         hipLaunchKernelGGL((k_count_chain_classes<NB, K, kClassWideBits>), g, b, 0, st,        \
                            d_x_off, d_z_off, n_shards, bags, p, cp, (const uint32_t*)work, o); \
@@ -1585,10 +1439,10 @@ static int64_t chain_planes_work_bytes(int64_t bags, int64_t max_nx, int64_t max
          (int64_t)sizeof(uint32_t);
 }
 
-// The count launch of the _planes entries on an output already zeroed: where
-// count_chain_launch would run k_count_chain_bits, the pre-pass and k_count_chain_planes
-// (the same tuning hook: R = largest groups per item) or, with class bits, its class-run form
-// (chainclass.h); everything else as count_chain_launch.
+// The count launch of the _planes entries on an output already zeroed: where chainplan.h's
+// chain_count_sliced says so, the pre-pass and k_count_chain_planes (tuning hook: R = largest
+// groups per item) or, with class bits, its class-run form (chainclass.h); everything else
+// count_chain_launch's packed kernel.
 static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, int64_t x_stride,
                                    const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                                    int32_t n_shards, int32_t steps, int64_t max_nx,
@@ -1596,10 +1450,10 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
                                    uint64_t* d_out, void* d_work, hipStream_t st) {
   const int64_t bags = (int64_t)n_shards * steps;
   if (max_nx == 0 || max_nz == 0) return TW_OK;
-  const int nb = plan_chain(max_nx, max_nz, bags, half != 0, bits_pick_nb(image_bound)).nb;
-  if (nb == 0)
+  const int nb = bits_pick_nb(image_bound);
+  if (!chain_count_sliced(max_nx, g_chain_R, half != 0, nb))
     return count_chain_launch(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride, n_shards,
-                              steps, max_nx, max_nz, half, -1, d_out, st);
+                              steps, max_nx, max_nz, half, d_out, st);
   // class bits: forced (clamped to this launch's planes), or chainclass.h's automatic rule
   const int k = g_class_bits < 0 ? class_bits_auto(max_nz, bags, nb)
                                  : std::min(g_class_bits, std::min(kClassMaxBits, nb - 8));
@@ -1608,9 +1462,8 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   const bool digits = k > 0 && class_loop_form(nb, k) == 3;
   int R = g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0;
   if (digits) R = R == 0 || R > kClassDigitsMaxR ? kClassDigitsMaxR : R;
-  // planes per digit: the wide split where this build has it and the hook's setting asks for it
-  const int dbits = digits && class_wide_built(nb, k) ? class_digit_bits(nb, k, g_class_digits)
-                                                      : kClassDigitBits;
+  // planes per digit: the wide split where it fits and the hook's setting asks for it
+  const int dbits = digits ? class_digit_bits(nb, k, g_class_digits) : kClassDigitBits;
   const int ndigits = dbits == kClassWideBits ? kClassWideDigits : kClassDigits;
   // (a padded slot's price in the swap rule is that of the loop this launch runs)
   const PlanesPlan p =
@@ -1655,8 +1508,8 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
 }
 }  // namespace tw
 
-// The loop form the class count of a launch with nb planes and k class bits runs in this build
-// (chainclass.h TW_CLASS_FORM; 3: the digit tables, where the low field fits them)
+// The loop form the class count of a launch with nb planes and k class bits runs (chainclass.h
+// class_loop_form; 3: the digit tables, where the low field fits them, 2: the masked planes)
 extern "C" int32_t tw_count_chain_class_form(int32_t nb, int32_t k) {
   return class_loop_form(nb, k);
 }
@@ -1686,9 +1539,8 @@ extern "C" int32_t tw_count_chain_class_digits(int32_t w) {
 // The planes per digit a launch of (nb, k) runs under the current setting: 4 where it runs the
 // wide digits, 3 everywhere else (where no digit loop runs the setting has no effect)
 extern "C" int32_t tw_count_chain_class_digits_of(int32_t nb, int32_t k) {
-  return k > 0 && class_loop_form(nb, k) == 3 && class_wide_built(nb, k)
-             ? class_digit_bits(nb, k, g_class_digits)
-             : kClassDigitBits;
+  return k > 0 && class_loop_form(nb, k) == 3 ? class_digit_bits(nb, k, g_class_digits)
+                                              : kClassDigitBits;
 }
 
 extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
@@ -1698,8 +1550,12 @@ extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, i
   return chain_planes_work_bytes((int64_t)n_shards * steps, max_nx, max_nz, half, image_bound);
 }
 
-// tw_count_pairs_chain_bound whose bit-sliced count reads planes built once per bag: the
-// pre-pass (k_chain_planes) and the count (k_count_chain_planes) back to back on the stream.
+// tw_count_pairs_chain with the caller's promise that every x and z image lies in
+// [0, image_bound] (x also: the -2^25 "never" image): the strict predicate with
+// image_bound < 2^24 runs bit-sliced where chain_count_sliced says so, on planes built once per
+// bag, everything else packed.  Same counts either way.  Bit-sliced: the pre-pass
+// (k_chain_planes) and the count (k_count_chain_planes or its class-run form) back to back on
+// the stream.
 // d_work: tw_chain_planes_work_bytes(...) bytes, written and read inside this call only.
 extern "C" int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d_x_off,
                                            int64_t x_stride, const void* d_z_bag,
@@ -1726,7 +1582,7 @@ extern "C" int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d
                                  d_work, st);
 }
 
-// tw_chain_unpack_count_bound with tw_count_pairs_chain_planes' count
+// tw_chain_unpack_count with tw_count_pairs_chain_planes' promise and count
 extern "C" int tw_chain_unpack_count_planes(const uint64_t* d_recv, int32_t world, int32_t steps,
                                             int64_t cap, int32_t half, int64_t n_x, int64_t n_z,
                                             int64_t x_shard, int64_t z_shard, int32_t n_shards,

@@ -454,56 +454,34 @@ TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb,
 }
 
 #if defined(__HIPCC__)
-// Build-time forms of the class loop (csrc/Makefile ab-classform):
-//   0  §4.1g's loop: bits_carry(G, P, c) per z, the images through a VGPR and v_readlane_b32
-//   1  masked low planes: the chain's carry is counted as it is, len * popc(G) once per item
-//   2  form 1 with the run read by scalar loads, TW_CLASS_BATCH images per load
-//   3  the digit tables (§4.1i) where the low field fits them (class_digits_fit(NB - K)):
-//      bits_count_span_digits; form 2 for every other (NB, K)
-#ifndef TW_CLASS_FORM
-#define TW_CLASS_FORM 3
-#endif
-// the form bits_count_class itself runs in: under form 3 it is the fallback, form 2
-#if TW_CLASS_FORM == 3
-#define TW_CLASS_BASE 2
-#else
-#define TW_CLASS_BASE TW_CLASS_FORM
-#endif
-#ifndef TW_CLASS_BATCH
-#define TW_CLASS_BATCH 4
-#endif
-static_assert(TW_CLASS_FORM >= 0 && TW_CLASS_FORM <= 3, "TW_CLASS_FORM: 0, 1, 2 or 3");
-static_assert(TW_CLASS_BATCH == 2 || TW_CLASS_BATCH == 4 || TW_CLASS_BATCH == 8 ||
-                  TW_CLASS_BATCH == 16,
-              "TW_CLASS_BATCH: a scalar load's width in words");
-// A scalar batch starts inside its run and may read up to TW_CLASS_BATCH - 1 words past the
-// run's end: into the same bag's later runs, the next bag's region or — from the last run of the
-// last bag — the entry counts, class_round64(n_bags) >= 64 words that follow the class-ordered
+// Images per scalar load of the masked-plane loop (widths 2, 8 and 16 lost: DESIGN §4.1h)
+constexpr int kClassBatch = 4;
+// A scalar batch starts inside its run and may read up to kClassBatch - 1 words past the run's
+// end: into the same bag's later runs, the next bag's region or — from the last run of the last
+// bag — the entry counts, class_round64(n_bags) >= 64 words that follow the class-ordered
 // region (class_plan: off_cnt = off_zs + n_bags * zs_stride).  Always inside the workspace; the
 // words read past the end are never compared.
-static_assert(TW_CLASS_BATCH - 1 < 64, "the over-read must stay inside the count region");
+static_assert(kClassBatch - 1 < 64, "the over-read must stay inside the count region");
 
-// One wave item: R groups of NB plane words per lane at pw (bits_count_planes' layout) against
-// the run's len >= 1 images at zs, complemented u32 of class cls (wave-uniform).  Exactly len
-// images are compared: a padded scalar slot would count G (form 0) or be missed by the
-// len * popc(G) term (forms 1, 2).
-//  Forms 0, 1: the images go 64 at a time through one VGPR, the next 64 in flight, and reach
-// the scalar side by v_readlane_b32 as in bits_scalar_loop; two per trip, an odd last one in a
-// step of its own.
-//  Form 2: zs is wave-uniform, so the run is read through the constant address space
-// (s_load_dwordxN straight into SGPRs): whole batches in an unrolled trip with the next batch
-// in flight, the last len mod TW_CLASS_BATCH images one at a time from the batch already loaded.
+// The masked-plane loop, the class loop of every (NB, K) whose low field the
+// digit tables do not take.  One wave item: R groups of NB plane words per lane at pw
+// (bits_count_planes' layout) against the run's len >= 1 images at zs, complemented u32 of
+// class cls (wave-uniform).  Once per item and group: G and P of the class from the K top
+// planes, the NL low planes ANDed with E = P & ~G, and popc(G) into ng.  Per z and group: the
+// low chain on the masked planes and one popcount of its carry; the class-constant term is
+// added once, as len * ng.  Exactly len images are evaluated: a padded scalar slot would be
+// missed by the len * ng term.
+//  zs is wave-uniform, so the run is read through the constant address space (s_load_dwordx4
+// straight into SGPRs): whole batches of kClassBatch images in an unrolled trip with the next
+// batch in flight, the last len mod kClassBatch images one at a time from the batch already
+// loaded.
 template <int NB, int K, int R>
 __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* __restrict__ pw,
                                                                const uint32_t* __restrict__ zs,
                                                                int len, uint32_t cls, int lane) {
   constexpr int NL = NB - K;
   uint32_t lo[R][NL], acc[R];
-#if TW_CLASS_BASE == 0
-  uint32_t G[R], P[R];
-#else
   uint32_t ng = 0;  // popc(G) over the groups: the class-constant term of one z
-#endif
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     uint32_t top[K];
@@ -511,14 +489,10 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
     for (int b = 0; b < NL; ++b) lo[r][b] = pw[(r * NB + b) * 64 + lane];
 #pragma unroll
     for (int b = 0; b < K; ++b) top[b] = pw[(r * NB + NL + b) * 64 + lane];
-#if TW_CLASS_BASE == 0
-    class_gp<K>(top, cls, G[r], P[r]);
-#else
     uint32_t g, p;
     class_gp<K>(top, cls, g, p);
     class_mask_planes<NL>(lo[r], class_equal_mask(g, p), lo[r]);
     ng = bits_popc_add(g, ng);
-#endif
     acc[r] = 0;
   }
   auto step = [&](uint32_t sc) {
@@ -532,15 +506,9 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
 #pragma unroll
       for (int r = 0; r < R; ++r) c[r] = bits_carry(lo[r][b], m[b], c[r]);
 #pragma unroll
-    for (int r = 0; r < R; ++r)
-#if TW_CLASS_BASE == 0
-      acc[r] = bits_popc_add(bits_carry(G[r], P[r], c[r]), acc[r]);
-#else
-      acc[r] = bits_popc_add(c[r], acc[r]);
-#endif
+    for (int r = 0; r < R; ++r) acc[r] = bits_popc_add(c[r], acc[r]);
   };
-#if TW_CLASS_BASE == 2
-  constexpr int B = TW_CLASS_BATCH;
+  constexpr int B = kClassBatch;
   typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
   const ConstWords zc = (ConstWords)(uintptr_t)zs;
   uint32_t cur[B], next[B];
@@ -562,51 +530,29 @@ __device__ __forceinline__ unsigned long long bits_count_class(const uint32_t* _
 #pragma unroll
     for (int u = 0; u + 1 < B; ++u) next[u] = next[u + 1];
   }
-#else
-  auto load = [&](int j) -> uint32_t { return zs[min(j + lane, len - 1)]; };  // (no branch)
-  uint32_t next = load(0);
-  for (int j = 0; j < len; j += 64) {
-    const uint32_t sv = next;
-    next = load(j + 64);
-    const int cnt = min(64, len - j);
-    int l = 0;
-    for (; l + 2 <= cnt; l += 2) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) step((uint32_t)__builtin_amdgcn_readlane((int)sv, l + u));
-    }
-    if (l < cnt) step((uint32_t)__builtin_amdgcn_readlane((int)sv, l));  // never a padded slot
-  }
-#endif
   unsigned long long tot = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) tot += acc[r];
-#if TW_CLASS_BASE != 0
   tot += (unsigned long long)(uint32_t)len * ng;  // the run's exact length
-#endif
   return tot;
 }
-// The loop form a launch of (nb, k) runs in this build
-constexpr int class_loop_form(int nb, int k) {
-  return TW_CLASS_FORM == 3 && !class_digits_fit(nb - k) ? 2 : TW_CLASS_FORM;
-}
-// Groups per item under the digit loop (build time: the register map of the largest sets the
-// kernel's VGPRs — 2: 4 waves per SIMD, 3: 3 waves, 4: 2 waves)
-#ifndef TW_CLASS_DIGIT_R
-#define TW_CLASS_DIGIT_R 2
-#endif
-static_assert(TW_CLASS_DIGIT_R >= 1 && TW_CLASS_DIGIT_R <= 4, "TW_CLASS_DIGIT_R: 1 .. 4");
-constexpr int kClassDigitsMaxR = TW_CLASS_DIGIT_R;
+// The loop a launch of (nb, k) runs: 3 the digit tables (§4.1i) where the low field fits
+// them, 2 the masked-plane loop everywhere else
+constexpr int class_loop_form(int nb, int k) { return class_digits_fit(nb - k) ? 3 : 2; }
+// Groups per item under the digit loops: their register maps hold two, which keeps 4 waves per
+// SIMD (3 and 4 groups — 3 and 2 waves — lost: DESIGN §4.1i)
+constexpr int kClassDigitsMaxR = 2;
 
-#if TW_CLASS_FORM == 3
 // The digit loop.  A group's tables sit in FIXED VGPRs and the hardware's VGPR
 // index mode picks the entry: between s_set_gpr_idx_on and _off, M0[7:0] — a z digit — is added
 // to the register numbers of a VALU instruction's first two sources (mode 0x3), so
 //     v_mov_b32    c, v24                     c = G0[d0]
 //     v_bitop3_b32 c, v32, v33, c  0xE8       c = majority(G1[d1], G1[d1 + 1], c)
 // read v(24 + d0) and v(32 + d1), v(33 + d1); the third source and the destination are not
-// indexed.  Register map: v8 .. v23 the carries of a batch (image u, group g: v(8 + 4u + g));
-// group g's 36 table registers from v(24 + 36g): digit 0 at + 0 (8 entries), digits 1, 2, 3 at
-// + 8, + 17, + 26 (9 entries each), one spare.
+// indexed.  Register map, two groups (g = 0, 1): v8 .. v23 the carries of a batch, four
+// registers per image of which the groups use the first two (image u, group g: v(8 + 4u + g));
+// group g's 36 table registers from v(24 + 36g) — digit 0 at + 0 (8 entries), digits 1, 2, 3 at
+// + 8, + 17, + 26 (9 entries each), one spare — so group 0 is v24 .. v59 and group 1 v60 .. v95.
 // Per z the scalar side shifts the digit-ready word (class_digit_encode) three times and sets
 // the index four times; per z and group the lane side issues 4 chain instructions and, after
 // _off — v_bcnt's operands would be indexed too — 1 popcount into the group's counter.  M0 and
@@ -619,27 +565,20 @@ constexpr int kClassDigitGroupRegs = 36;
 static_assert(class_digit_table_regs(kClassDigitMaxNL) <= kClassDigitGroupRegs, "register map");
 // flat register of entry d of digit j inside a group's 36
 constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1) + d; }
+static_assert(kClassDigitsMaxR == 2, "the registers named below: two groups, v24 .. v95");
 
 #define TW_DG_OP(C, A, B) "v_bitop3_b32 " C ", " A ", " B ", " C " bitop3:0xe8\n\t"
 #define TW_DG_MOV(C, A) "v_mov_b32 " C ", " A "\n\t"
 #define TW_DG_IDX(Z, T, SH) "s_lshr_b32 " T ", " Z ", " SH "\n\ts_set_gpr_idx_idx " T "\n\t"
-// digit steps of the groups: carry registers C0 .. C3 of one image
+// digit steps of the groups: C0 .. C3 the carry registers of one image (groups: C0, C1)
 #define TW_DG_D0_1(C0, C1, C2, C3) TW_DG_MOV(C0, "v24")
 #define TW_DG_D0_2(C0, C1, C2, C3) TW_DG_D0_1(C0, C1, C2, C3) TW_DG_MOV(C1, "v60")
-#define TW_DG_D0_3(C0, C1, C2, C3) TW_DG_D0_2(C0, C1, C2, C3) TW_DG_MOV(C2, "v96")
-#define TW_DG_D0_4(C0, C1, C2, C3) TW_DG_D0_3(C0, C1, C2, C3) TW_DG_MOV(C3, "v132")
 #define TW_DG_D1_1(C0, C1, C2, C3) TW_DG_OP(C0, "v32", "v33")
 #define TW_DG_D1_2(C0, C1, C2, C3) TW_DG_D1_1(C0, C1, C2, C3) TW_DG_OP(C1, "v68", "v69")
-#define TW_DG_D1_3(C0, C1, C2, C3) TW_DG_D1_2(C0, C1, C2, C3) TW_DG_OP(C2, "v104", "v105")
-#define TW_DG_D1_4(C0, C1, C2, C3) TW_DG_D1_3(C0, C1, C2, C3) TW_DG_OP(C3, "v140", "v141")
 #define TW_DG_D2_1(C0, C1, C2, C3) TW_DG_OP(C0, "v41", "v42")
 #define TW_DG_D2_2(C0, C1, C2, C3) TW_DG_D2_1(C0, C1, C2, C3) TW_DG_OP(C1, "v77", "v78")
-#define TW_DG_D2_3(C0, C1, C2, C3) TW_DG_D2_2(C0, C1, C2, C3) TW_DG_OP(C2, "v113", "v114")
-#define TW_DG_D2_4(C0, C1, C2, C3) TW_DG_D2_3(C0, C1, C2, C3) TW_DG_OP(C3, "v149", "v150")
 #define TW_DG_D3_1(C0, C1, C2, C3) TW_DG_OP(C0, "v50", "v51")
 #define TW_DG_D3_2(C0, C1, C2, C3) TW_DG_D3_1(C0, C1, C2, C3) TW_DG_OP(C1, "v86", "v87")
-#define TW_DG_D3_3(C0, C1, C2, C3) TW_DG_D3_2(C0, C1, C2, C3) TW_DG_OP(C2, "v122", "v123")
-#define TW_DG_D3_4(C0, C1, C2, C3) TW_DG_D3_3(C0, C1, C2, C3) TW_DG_OP(C3, "v158", "v159")
 // one image against R groups; the index already holds its digit 0
 #define TW_DG_Z(R, Z, T, C0, C1, C2, C3)                        \
   TW_DG_D0_##R(C0, C1, C2, C3)                                  \
@@ -650,8 +589,6 @@ constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1
 #define TW_DG_CNT(C, A) "v_bcnt_u32_b32 " A ", " C ", " A "\n\t"
 #define TW_DG_C_1(C0, C1, C2, C3) TW_DG_CNT(C0, "%[a0]")
 #define TW_DG_C_2(C0, C1, C2, C3) TW_DG_C_1(C0, C1, C2, C3) TW_DG_CNT(C1, "%[a1]")
-#define TW_DG_C_3(C0, C1, C2, C3) TW_DG_C_2(C0, C1, C2, C3) TW_DG_CNT(C2, "%[a2]")
-#define TW_DG_C_4(C0, C1, C2, C3) TW_DG_C_3(C0, C1, C2, C3) TW_DG_CNT(C3, "%[a3]")
 #define TW_DG_ONE(R)                                            \
   "s_set_gpr_idx_on %[z0], 0x3\n\t"                             \
   TW_DG_Z(R, "%[z0]", "%[t]", "v8", "v9", "v10", "v11") "s_set_gpr_idx_off\n\t" \
@@ -669,8 +606,6 @@ constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1
   "s_waitcnt lgkmcnt(0)"
 #define TW_DG_ACC_1(a) [a0] "+v"(a[0])
 #define TW_DG_ACC_2(a) TW_DG_ACC_1(a), [a1] "+v"(a[1])
-#define TW_DG_ACC_3(a) TW_DG_ACC_2(a), [a2] "+v"(a[2])
-#define TW_DG_ACC_4(a) TW_DG_ACC_3(a), [a3] "+v"(a[3])
 // (s_lshr_b32 writes SCC: without the clobber a compare is scheduled across the statement)
 #define TW_DG_CARRIES1 "scc", "v8", "v9", "v10", "v11"
 #define TW_DG_CARRIES4                                                                   \
@@ -678,8 +613,6 @@ constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1
       "v22", "v23"
 #define TW_DG_TAB_1(a, b) "{v[24:55]}"(a[0]), "{v[56:59]}"(b[0])
 #define TW_DG_TAB_2(a, b) TW_DG_TAB_1(a, b), "{v[60:91]}"(a[1]), "{v[92:95]}"(b[1])
-#define TW_DG_TAB_3(a, b) TW_DG_TAB_2(a, b), "{v[96:127]}"(a[2]), "{v[128:131]}"(b[2])
-#define TW_DG_TAB_4(a, b) TW_DG_TAB_3(a, b), "{v[132:163]}"(a[3]), "{v[164:167]}"(b[3])
 #define TW_DG_CASE_BATCH(R)                                                                \
   if constexpr (kR == R)                                                                   \
     asm volatile(TW_DG_BATCH(R)                                                            \
@@ -706,7 +639,7 @@ constexpr int class_digit_reg(int j, int d) { return j == 0 ? d : 8 + 9 * (j - 1
 // (two statements per trip, the batches' registers swapping roles); the last len mod 4 images
 // one statement each from the batch already loaded, so exactly len images are evaluated and no
 // word past the run's end reaches M0.  A whole batch's load reads up to four words past the
-// run's end (never used): inside the workspace, as in form 2.
+// run's end (never used): inside the workspace, as in bits_count_class.
 //  The lane sums are u32 over the whole span: see kClassMaxBagZ.
 constexpr int kClassDigitBatch = 4;  // images per statement and scalar load
 static_assert(kClassDigitBatch < 64, "the over-read must stay inside the count region");
@@ -764,7 +697,7 @@ __device__ __forceinline__ unsigned long long bits_count_span_digits(
   auto batch = [&](const ClassVec4 z, ConstWords nz, ClassVec4& next) {
 #if defined(__HIP_DEVICE_COMPILE__)
     uint32_t t;
-    TW_DG_CASE_BATCH(1) TW_DG_CASE_BATCH(2) TW_DG_CASE_BATCH(3) TW_DG_CASE_BATCH(4)
+    TW_DG_CASE_BATCH(1) TW_DG_CASE_BATCH(2)
 #else
     next = z;
 #endif
@@ -772,7 +705,7 @@ __device__ __forceinline__ unsigned long long bits_count_span_digits(
   auto one = [&](uint32_t z) {
 #if defined(__HIP_DEVICE_COMPILE__)
     uint32_t t;
-    TW_DG_CASE_ONE(1) TW_DG_CASE_ONE(2) TW_DG_CASE_ONE(3) TW_DG_CASE_ONE(4)
+    TW_DG_CASE_ONE(1) TW_DG_CASE_ONE(2)
 #endif
   };
   uint32_t ng = 0, cg = 0;  // popc(G) over the groups of the class at hand; sum of len * ng
@@ -838,16 +771,14 @@ __device__ __forceinline__ unsigned long long bits_count_span_digits_of(
 }
 
 // The wide-digit loop: bits_count_span_digits on the three 4-plane digits of a
-// 12-plane low field (class_wide_*), built where the register map holds the groups of an item
-// (TW_CLASS_DIGIT_R <= kClassWideMaxR).  Per z the scalar side shifts the word twice and sets the
-// index three times (5 SALU, not 7); per z and group the lane side issues one v_mov, two
-// v_bitop3 and one v_bcnt (4 VALU, not 5).  Register map: v8 .. v15 the carries of a batch
+// 12-plane low field (class_wide_*); its register map holds the kClassDigitsMaxR groups of an
+// item.  Per z the scalar side shifts the word twice and sets the index three times (5 SALU,
+// not 7); per z and group the lane side issues one v_mov, two v_bitop3 and one v_bcnt (4 VALU,
+// not 5).  Register map: v8 .. v15 the carries of a batch
 // (image u, group g: v(8 + 2u + g)); group g's 50 table registers from v(24 + 50g): digit 0 at
 // + 0 (16 entries), digits 1 and 2 at + 16 and + 33 (17 entries each); two groups end at v123.
 // Only words pre-pass 2 wrote with class_wide_encode reach M0: every digit is below 16, so an
 // indexed read of entries d and d + 1 stays inside its table.
-#define TW_CLASS_WIDE (TW_CLASS_DIGIT_R <= 2)
-#if TW_CLASS_WIDE
 typedef uint32_t ClassVec2 __attribute__((ext_vector_type(2)));
 typedef uint32_t ClassVec16 __attribute__((ext_vector_type(16)));
 static_assert(kClassDigitsMaxR <= kClassWideMaxR, "the wide register map holds two groups");
@@ -1024,16 +955,6 @@ __device__ __forceinline__ unsigned long long bits_count_span_wide_of(
   if constexpr (R > 1)
     if (ng < R) return bits_count_span_wide_of<NB, K, R - 1>(pw, zbag, tab, n, lane, ng);
   return bits_count_span_wide<NB, K, R>(pw, zbag, tab, n, lane);
-}
-#endif  // TW_CLASS_WIDE
-#endif  // TW_CLASS_FORM == 3
-// Whether this build has the wide-digit loop for a launch of (nb, k)
-constexpr bool class_wide_built(int nb, int k) {
-#if TW_CLASS_FORM == 3 && TW_CLASS_DIGIT_R <= 2
-  return class_wide_fit(nb - k);
-#else
-  return false;
-#endif
 }
 #endif  // __HIPCC__
 

@@ -4,7 +4,7 @@
 // A bag's bit planes (bitcount.h) are built ONCE per launch by a pre-pass, in groups of
 // kPlaneGroup images, and the count's items read them:
 //  * a PLANE item: up to R consecutive x groups (lane side) against one z chunk (the
-//    wave-uniform scalar side) — the item of k_count_chain_bits without its transposes;
+//    wave-uniform scalar side);
 //  * a SWAPPED item, for the x remainder rx = nx mod kPlaneGroup: x > z is the carry out of
 //    x + ~z, symmetric in its operands, so the remainder's x images are the scalars
 //    (uncomplemented; NaN and "never" images 0, which carry against nothing) and up to R
@@ -53,6 +53,30 @@ struct PlanesPlan {
 };
 
 TW_BITS_HD int64_t planes_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Whether a launch counts bit-sliced (on planes) or with the packed kernel (k_count_chain).
+// nb: bits_pick_nb of the caller's image bound (0: none promised, or none below 2^24); forced_R:
+// tw_count_chain_set_plan's R (0 automatic; 8, 16 force the packed kernel, 2 .. 4 the planes).
+// Bit-sliced needs the strict predicate and nb > 0.  Under the automatic plan a bag much
+// smaller than a plane tile pads more slots than the bit-sliced loop gains (1.39x per slot,
+// profiles/r07_mb_bits.log): the least slots of tiles of 2 or 4 groups — max_nx rounded up to
+// the tile — past kBitsMaxPad x the least slots of the packed kernel's 16 or 8 images per lane
+// keep the launch packed.  Interleaved A/B against the packed kernel (tools/count_bits_ab.py,
+// profiles/r07_count_bits_ab.json): headline K = 20 8.48 -> 5.77 ms, K = 32 13.26 -> 9.07,
+// K = 4 1.79 -> 1.19; per-rank shapes G = 2 / 4 / 8 at K = 20 0.66-0.67 of the packed time, C2
+// (one 1e5 x 1e5 bag) 0.294 -> 0.260; none slower.
+constexpr double kBitsMaxPad = 1.25;
+TW_BITS_HD int64_t planes_padded(int64_t n, int64_t tile) {  // n rounded up to whole tiles
+  return planes_ceil_div(n, tile) * tile;
+}
+TW_BITS_HD bool chain_count_sliced(int64_t max_nx, int forced_R, bool half, int nb) {
+  if (half || nb <= 0 || forced_R == 8 || forced_R == 16) return false;
+  if (forced_R != 0) return true;
+  const int64_t p16 = planes_padded(max_nx, 64 * 16), p8 = planes_padded(max_nx, 64 * 8);
+  const int64_t s2 = planes_padded(max_nx, 2 * kPlaneGroup);
+  const int64_t s4 = planes_padded(max_nx, 4 * kPlaneGroup);
+  return (double)(s2 < s4 ? s2 : s4) <= kBitsMaxPad * (double)(p16 < p8 ? p16 : p8);
+}
 
 // R, z_chunk: 0 = automatic (R = 4); swap: 0 never, 1 by the rule above, 2 always
 TW_BITS_HD PlanesPlan planes_plan(int64_t max_nx, int64_t max_nz, int64_t n_bags, int R,
