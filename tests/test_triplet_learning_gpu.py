@@ -1,9 +1,10 @@
 """tuplewise.triplet_learning on the device against the NumPy oracle of
 tests/test_triplet_learning_cpu.py: the projection bit for bit, the loss and the gradient within
-the project's bound for unpinned gradients at every kernel instantiation and
-around the slice of triplets one workgroup takes, the counts of active triplets exactly, the
-update bit for bit, and whole trajectories with their evaluations, RNG consumption and untouched
-inputs."""
+the project's bound for unpinned gradients at d, p in {1, 3, 8, 17, 33, 64} — the
+DP, PP in {8, 32, 64} forms of k_triplet_grad, 7 of the 16 pairs with the gradient and 4 without;
+tests/test_triplet_learning_gpu_forms.py runs all 32 — and around the slice of triplets one
+workgroup takes, the counts of active triplets exactly, the update bit for bit, and whole
+trajectories with their evaluations, RNG consumption and untouched inputs."""
 import functools
 
 import numpy as np
