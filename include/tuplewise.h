@@ -181,6 +181,35 @@ int tw_chain_emit(const uint64_t* d_x_rec, int64_t n_x, const uint64_t* d_z_rec,
                   int32_t steps, int64_t x_shard, int64_t z_shard, int32_t n_shards,
                   void* d_x_bag, void* d_z_bag, uint32_t* d_cursors, uint64_t* d_send,
                   int64_t cap, int32_t* d_flag, void* stream);
+/* tw_chain_emit with round tables: where both permutation domains are small
+ * enough (world * n_x and world * n_z <= 2^22) the six Feistel round functions of every (step,
+ * class) are tabulated once per call into d_work and each block looks its rounds up in LDS —
+ * the same permutations bit for bit, without the rounds' multiplies.  d_work: caller-provided,
+ * 16-B aligned, at least tw_chain_emit_work_bytes(steps, world * n_x, world * n_z) bytes (else
+ * TW_ERR_ARG before any launch); written and read inside this one call on this one stream, so
+ * calls on one stream may reuse it and calls on different streams need their own.  Larger
+ * domains (work bytes 0) run tw_chain_emit's arithmetic rounds; tw_chain_emit itself always
+ * does. */
+int tw_chain_emit_ws(const uint64_t* d_x_rec, int64_t n_x, const uint64_t* d_z_rec, int64_t n_z,
+                     int32_t half, uint32_t* d_x_pos, uint32_t* d_z_pos, int32_t first,
+                     int32_t rank, int32_t world, const uint64_t* keys_x, const uint64_t* keys_z,
+                     int32_t steps, int64_t x_shard, int64_t z_shard, int32_t n_shards,
+                     void* d_x_bag, void* d_z_bag, uint32_t* d_cursors, uint64_t* d_send,
+                     int64_t cap, int32_t* d_flag, void* d_work, int64_t work_bytes,
+                     void* stream);
+int64_t tw_chain_emit_work_bytes(int32_t steps, int64_t NX, int64_t NZ);
+/* Tuning hook for tw_chain_emit_ws's round tables: 0 automatic (one process with strict ties,
+ * 8 elements per thread, one step per round, domains up to 2^20: where the sweep of DESIGN
+ * §4.1c found them faster), 1 off (the arithmetic rounds), 2 on wherever a table fits; -1
+ * reports.  Returns the previous setting; any other value is TW_ERR_ARG (tw_last_error names
+ * it) and changes nothing.  Process-global; results do not depend on it. */
+int32_t tw_chain_set_emit_tables(int32_t mode);
+/* 1 where the tw_chain_emit_ws launch with these arguments (exchange: d_send given) looks its
+ * rounds up under the current settings (this hook and tw_chain_set_emit), 0 where it runs the
+ * arithmetic rounds: the launch's own decision.  Under the automatic rule half ties, the
+ * exchange and more than 512 buckets run the arithmetic rounds. */
+int32_t tw_chain_emit_tables_of(int64_t n_x, int64_t n_z, int32_t world, int32_t half,
+                                int32_t exchange, int32_t n_shards);
 /* The receiving side of tw_chain_emit's buckets after an equal-split all-to-all (d_recv: world
  * chunks in source order): every record appended to the bag region of its (step, side, shard)
  * — shard b of a side holds positions [min(b k, n), min((b+1) k, n)), k = x_shard / z_shard,

@@ -1,5 +1,5 @@
 """Kernel timeline of the chain probe's rank calls (tools/chain_probe.py under rocprofv3
---kernel-trace): the trace cut into calls at each ranking or, carried, at each k_chain_zero_heads (the
+--kernel-trace): the trace cut into calls at each ranking or, carried, at each k_chain_emit_prep (the
 first kernel of an over-ranks emission), each call's kernels with their start offsets and durations, and per
 kernel the median duration over the calls without a ranking (the carried calls) — what the
 probe's HIP-event parts time beside what the device spent inside each kernel; the difference is
@@ -18,15 +18,15 @@ calls, cur = [], None
 for r in rows:
     name = short(r)
     # a call starts at its ranking (k_rank_sample_*) or, carried, at its zero_heads
-    if "k_rank_sample" in name or ("k_chain_zero_heads" in name and (
-            cur is None or any("k_chain_zero_heads" in n for n, _, _ in cur))):
+    if "k_rank_sample" in name or ("k_chain_emit_prep" in name and (
+            cur is None or any("k_chain_emit_prep" in n for n, _, _ in cur))):
         cur = []
         calls.append(cur)
     if cur is not None:
         cur.append((name, int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
 out = []
 per = {}
-calls = [c for c in calls if any("k_chain_zero_heads" in n for n, _, _ in c)]  # over ranks
+calls = [c for c in calls if any("k_chain_emit_prep" in n for n, _, _ in c)]  # over ranks
 for i, c in enumerate(calls):
     t0 = c[0][1]
     ranked = any("rank" in n for n, _, _ in c)

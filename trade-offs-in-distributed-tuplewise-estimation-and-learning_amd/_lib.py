@@ -52,6 +52,11 @@ _SIGNATURES = {
                              _vp],
     "tw_chain_emit": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32,
                       _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "tw_chain_emit_ws": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32,
+                         _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    "tw_chain_emit_work_bytes": [_i32, _i64, _i64],
+    "tw_chain_set_emit_tables": [_i32],
+    "tw_chain_emit_tables_of": [_i64, _i64, _i32, _i32, _i32, _i32],
     "tw_chain_unpack": [_vp, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp,
                         _vp],
     "tw_count_pairs_chain": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i32, _vp,
@@ -282,6 +287,7 @@ _RESTYPES = {
     "tw_self_pairs_idx_work_bytes": ctypes.c_int64,
     "tw_self_sorted_work_bytes": ctypes.c_int64,
     "tw_chain_planes_work_bytes": ctypes.c_int64,
+    "tw_chain_emit_work_bytes": ctypes.c_int64,
     "tw_triplet_idx_work_bytes": ctypes.c_int64,
     "tw_triplet_grad_work_bytes": ctypes.c_int64,
 }

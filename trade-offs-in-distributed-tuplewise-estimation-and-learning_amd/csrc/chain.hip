@@ -80,6 +80,15 @@ struct ChainEmit {
   int64_t cap;
   int* flag;
   int bx;  // blocks of X tiles; the rest are Z tiles
+  // round tables (feistel.h; null: the arithmetic rounds): per (step, class) tab_stride
+  // entries, class X first; hbx / hbz: the classes' half_bits
+  const uint16_t* tab;
+  uint32_t tab_stride, hbx, hbz;
+};
+
+// the round keys of a chunk's Feistel networks (host-made: k_chain_emit_prep's arguments)
+struct ChainRounds {
+  uint32_t k[kChainMax][2][6];
 };
 
 __device__ __forceinline__ int64_t em_region(int b, uint32_t k, int64_t n) {
@@ -91,13 +100,14 @@ __device__ __forceinline__ int64_t em_region(int b, uint32_t k, int64_t n) {
 // (4.6 % of the slots at n = 1e6 on a 2^20 domain) lane by lane — each lane takes ITS next
 // walking slot, so a wave re-evaluates max-over-lanes times instead of once per slot with a
 // walker anywhere in the wave (~0.95 of the slots)
-template <int EPR>
-__device__ __forceinline__ void chain_next(const Feistel& F, uint32_t Ntot, uint32_t (&pos)[EPR],
+// (once: one round set on a position — the arithmetic rounds or the table's)
+template <int EPR, class Once>
+__device__ __forceinline__ void chain_next(Once once, uint32_t Ntot, uint32_t (&pos)[EPR],
                                            unsigned valid) {
   unsigned walk = 0;
 #pragma unroll
   for (int r = 0; r < EPR; ++r) {
-    pos[r] = feistel_once32(F, pos[r]);
+    pos[r] = once(pos[r]);
     if (((valid >> r) & 1u) && pos[r] >= Ntot) walk |= 1u << r;
   }
   while (__any(walk != 0)) {
@@ -106,7 +116,7 @@ __device__ __forceinline__ void chain_next(const Feistel& F, uint32_t Ntot, uint
       uint32_t v = pos[0];
 #pragma unroll
       for (int i = 1; i < EPR; ++i) v = i == r ? pos[i] : v;
-      v = feistel_once32(F, v);
+      v = once(v);
 #pragma unroll
       for (int i = 0; i < EPR; ++i) pos[i] = i == r ? v : pos[i];
       if (v < Ntot) walk &= ~(1u << r);
@@ -123,15 +133,34 @@ __device__ __forceinline__ void chain_next(const Feistel& F, uint32_t Ntot, uint
 // kept in memory and placed by a second, fully parallel pass measured slower in both regimes
 // (2e6 elements x 20 steps: 308 against 254 us; 250k: 59 against 52 us;
 // profiles/r04_prof_parts3_stats.log) — it re-reads the images once per step.
-template <int EPR, int S, bool STAGED>
+//
+// FULL: the staging of every mode (8-B values for half ties' {g, h} images, the exchange's
+// position word).  One process with strict ties stages 4-B values only (FULL = false), which
+// leaves the LDS for the round table below without costing a resident block.
+//
+// Round tables (em.tab, feistel.h): the block keeps the current step's table of its class in
+// dynamic LDS, copied from the launch's workspace (k_chain_emit_prep) with 16-B loads.  A
+// step's table is dead once every thread has left chain_next — after the round's first
+// barrier — so the next step's copy is issued there and is visible after the round's later
+// barriers: no barrier is added at one step per round.  With several steps per round each
+// further step of the round pays two barriers around its copy.
+//
+// Destinations: the reservation loop has (step, bucket) of every counter anyway, so it leaves
+// the counter's destination in LDS (dst: one process, the element offset c n + region(b) +
+// reserved; the exchange, the record slot (b steps + c)(cap + 1) + 1 + reserved) and a staged
+// record costs one LDS read, one add and the store — no division, no 64-bit multiply.
+template <int EPR, int S, bool STAGED, bool FULL>
 __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKeys keys) {
   constexpr int TILE = kEmThreads * EPR;
   constexpr int MB = STAGED ? kEmMaxB : kEmMaxBig;
+  using SV = std::conditional_t<FULL, uint64_t, uint32_t>;
+  extern __shared__ uint4 tabq[];
   __shared__ Feistel fs[kChainMax];
-  __shared__ unsigned hist[MB], base[MB], start[STAGED ? kEmMaxB : 1];
+  __shared__ unsigned hist[MB], base[STAGED && !FULL ? 1 : MB], start[STAGED ? kEmMaxB : 1];
+  __shared__ uint64_t dst[STAGED ? kEmMaxB : 1];
   __shared__ unsigned wave_tot[kEmThreads / kWave];
-  __shared__ uint64_t sv[STAGED ? TILE * S : 1];
-  __shared__ uint32_t sq[STAGED ? TILE * S : 1];
+  __shared__ SV sv[STAGED ? TILE * S : 1];
+  __shared__ uint32_t sq[STAGED && FULL ? TILE * S : 1];
   __shared__ uint16_t sb[STAGED ? TILE * S : 1];
   const bool isx = (int)blockIdx.x < em.bx;
   const int tile = isx ? (int)blockIdx.x : (int)blockIdx.x - em.bx;
@@ -143,8 +172,19 @@ __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKe
   const uint64_t* rec = isx ? em.xr : em.zr;
   uint32_t* posa = isx ? em.xpos : em.zpos;
   const int64_t gbase = isx ? em.xbase : em.zbase;
-  const bool wide = isx && em.half;  // 8-B x images {g, h}
-  uint64_t val[EPR];
+  const bool xchg = FULL && em.xchg;
+  const bool wide = FULL && isx && em.half;  // 8-B x images {g, h}
+  const uint16_t* tab = (const uint16_t*)tabq;
+  const bool tabs = em.tab != nullptr;
+  const uint32_t hb = isx ? em.hbx : em.hbz, hmask = (1u << hb) - 1;
+  auto tab_load = [&](int c) {  // step c's table of this class (tab_stride covers the pad)
+    const uint4* src =
+        (const uint4*)(em.tab + ((size_t)c * 2 + (isx ? 0 : 1)) * em.tab_stride);
+    const int nq = (int)(((6u << hb) + 7) / 8);
+    for (int q = threadIdx.x; q < nq; q += kEmThreads) tabq[q] = src[q];
+  };
+  if (tabs) tab_load(0);
+  SV val[EPR];
   uint32_t pos[EPR];
   unsigned valid = 0;
   const int64_t e0 = (int64_t)tile * TILE + threadIdx.x;
@@ -156,12 +196,12 @@ __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKe
     if (e < n) {
       valid |= 1u << r;
       const uint64_t v = rec[e];
-      val[r] = wide ? v : (v & 0xFFFFFFFFull);
+      val[r] = (SV)(wide ? v : (v & 0xFFFFFFFFull));
       pos[r] = em.first ? (uint32_t)(gbase + e) : posa[e];
     }
   }
   const int N = em.nsh;
-  const int NB = em.xchg ? em.world : N + 1;
+  const int NB = xchg ? em.world : N + 1;
   const uint32_t kb = (uint32_t)(isx ? em.kx : em.kz);
   const FastDiv dk = isx ? em.dkx : em.dkz;
   const FastDiv dn = isx ? em.dnx : em.dnz;
@@ -182,13 +222,25 @@ __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKe
         slot[s][r] = 0;
       }
       if (s < ns) {
-        chain_next<EPR>(fs[c0 + s], (uint32_t)Ntot, pos, valid);
+        if (tabs) {
+          if (S > 1 && s > 0) {  // (block-uniform) the round's further steps: their own copy
+            __syncthreads();
+            tab_load(c0 + s);
+            __syncthreads();
+          }
+          chain_next<EPR>([&](uint32_t v) { return feistel_once32_tab(tab, hb, hmask, v); },
+                          (uint32_t)Ntot, pos, valid);
+        } else {
+          const Feistel& F = fs[c0 + s];
+          chain_next<EPR>([&](uint32_t v) { return feistel_once32(F, v); }, (uint32_t)Ntot, pos,
+                          valid);
+        }
 #pragma unroll
         for (int r = 0; r < EPR; ++r) {
           if ((valid >> r) & 1u) {
             const uint32_t q = pos[r];
             int b;
-            if (em.xchg) {
+            if (xchg) {
               const uint32_t g = fast_div32(q, dn);
               const uint32_t ql = q - g * (uint32_t)n;
               b = (int)g;
@@ -203,26 +255,34 @@ __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKe
       }
     }
     __syncthreads();
+    // every thread has left chain_next: the table is dead, the next round's first copy goes
+    if (tabs && c0 + ns < em.steps) tab_load(c0 + ns);
     const int nc = ns * NB;
     for (int i = threadIdx.x; i < nc; i += kEmThreads) {
-      const int s = i / NB, b = i - s * NB;
+      const int s = S == 1 ? 0 : i / NB, b = i - s * NB;
       const int c = c0 + s;
       const unsigned h = hist[i];
       unsigned* cu;
-      if (em.xchg)
+      if (xchg)
         cu = (unsigned*)(em.send + ((int64_t)b * em.steps + c) * (em.cap + 1) * em.W);
       else
         cu = em.cur + ((int64_t)c * 2 + (isx ? 0 : 1)) * (N + 1) + b;
-      base[i] = h ? atomicAdd(cu, h) : 0u;
-      if constexpr (STAGED) start[i] = h;
+      const unsigned got = h ? atomicAdd(cu, h) : 0u;
+      if constexpr (!STAGED || FULL) base[i] = got;
+      if constexpr (STAGED) {
+        start[i] = h;
+        dst[i] = xchg ? (uint64_t)(((int64_t)b * em.steps + c) * (em.cap + 1) + 1 + got)
+                      : (uint64_t)((int64_t)c * n + em_region(b, kb, n) + got);
+      }
       hist[i] = 0;  // for the next round (its atomics come after the next barrier)
     }
     __syncthreads();
-    // one record: counter i = s * NB + b (step c0 + s, bucket b), slot u in the bucket's run
+    // one record of the unstaged form: counter i = s * NB + b (step c0 + s, bucket b), slot u
+    // in the bucket's run
     auto put = [&](int i, unsigned u, uint64_t v, uint32_t a) {
-      const int s = i / NB, b = i - s * NB;
+      const int s = S == 1 ? 0 : i / NB, b = i - s * NB;
       const int c = c0 + s;
-      if (em.xchg) {
+      if (xchg) {
         if ((int64_t)u >= em.cap) {
           *em.flag = 1;  // dropped, never written out of place; the host raises
           return;
@@ -251,16 +311,35 @@ __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKe
           if (bk[s][r] < 0) continue;
           const unsigned j = start[bk[s][r]] + slot[s][r];
           sv[j] = val[r];
-          sq[j] = aux[s][r];
+          if constexpr (FULL) sq[j] = aux[s][r];
           sb[j] = (uint16_t)bk[s][r];
         }
       }
       __syncthreads();
+      // a staged record: its counter's destination (dst) plus its place in the counter's run
       for (int j = threadIdx.x; j < cnt * ns; j += kEmThreads) {
         const int i = sb[j];
-        put(i, base[i] + (unsigned)j - start[i], sv[j], sq[j]);
+        const unsigned rel = (unsigned)j - start[i];
+        const uint64_t o = dst[i] + rel;
+        if (xchg) {
+          if ((int64_t)base[i] + rel >= em.cap) {
+            *em.flag = 1;  // dropped, never written out of place; the host raises
+            continue;
+          }
+          const uint64_t v = sv[j];
+          if (em.W == 1) {
+            em.send[o] = v | ((uint64_t)sq[FULL ? j : 0] << 32);
+          } else {
+            em.send[2 * o] = v;
+            em.send[2 * o + 1] = sq[FULL ? j : 0];
+          }
+        } else if (wide) {
+          ((uint64_t*)em.xbag)[o] = sv[j];
+        } else {
+          (isx ? (uint32_t*)em.xbag : em.zbag)[o] = (uint32_t)sv[j];
+        }
       }
-      __syncthreads();  // staging and start[] are reused by the next round
+      __syncthreads();  // staging, start[] and dst[] are reused by the next round
     } else {
 #pragma unroll
       for (int s = 0; s < S; ++s)
@@ -276,12 +355,28 @@ __global__ __launch_bounds__(kEmThreads) void k_chain_emit(ChainEmit em, ChainKe
   }
 }
 
-// the count slots of every (destination, step) bucket of a send buffer
-__global__ __launch_bounds__(kBlock) void k_chain_zero_heads(uint64_t* __restrict__ send,
-                                                             int64_t buckets, int64_t stride) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < buckets;
-       i += (int64_t)gridDim.x * kBlock)
-    send[i * stride] = 0;
+// What an emission launch needs beforehand, in ONE launch: the cursors (one process: `words`
+// 4-B words at `zero`) or the send heads (the exchange: `words` buckets of `stride` 8-B words)
+// zeroed, and — with round tables — the chunk's tables: blockIdx.y = 2 step + class, F_i(R)
+// at tab[blockIdx.y * tab_stride + (i << hb) + R] (the pad up to tab_stride is never looked up).
+__global__ __launch_bounds__(kBlock) void k_chain_emit_prep(void* __restrict__ zero, int64_t words,
+                                                            int64_t stride, ChainRounds rk,
+                                                            uint16_t* __restrict__ tab,
+                                                            uint32_t tab_stride, uint32_t hbx,
+                                                            uint32_t hbz) {
+  const int64_t t0 = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+  const int64_t nt = (int64_t)gridDim.x * gridDim.y * kBlock;
+  if (stride == 0) {
+    for (int64_t i = t0; i < words; i += nt) ((unsigned*)zero)[i] = 0;
+  } else {
+    for (int64_t i = t0; i < words; i += nt) ((uint64_t*)zero)[i * stride] = 0;
+  }
+  if (tab == nullptr) return;
+  const int c = blockIdx.y >> 1, cls = blockIdx.y & 1;
+  const uint32_t hb = cls ? hbz : hbx, mask = (1u << hb) - 1;
+  uint16_t* out = tab + (size_t)blockIdx.y * tab_stride;
+  for (uint32_t e = blockIdx.x * kBlock + threadIdx.x; e < (6u << hb); e += gridDim.x * kBlock)
+    out[e] = feistel_round_value(e & mask, rk.k[c][cls][e >> hb], mask);
 }
 
 // Receiver side: every record of bucket (source g, step c) appended to its (step, side, shard)
@@ -1018,13 +1113,57 @@ static ChainKeys chain_keys(const uint64_t* kx, const uint64_t* kz, int steps) {
 
 using namespace tw;
 
-extern "C" int tw_chain_emit(const uint64_t* d_x_rec, int64_t n_x, const uint64_t* d_z_rec,
-                             int64_t n_z, int32_t half, uint32_t* d_x_pos, uint32_t* d_z_pos,
-                             int32_t first, int32_t rank, int32_t world, const uint64_t* keys_x,
-                             const uint64_t* keys_z, int32_t steps, int64_t x_shard,
-                             int64_t z_shard, int32_t n_shards, void* d_x_bag, void* d_z_bag,
-                             uint32_t* d_cursors, uint64_t* d_send, int64_t cap,
-                             int32_t* d_flag, void* stream) {
+// Round tables of the emission (tw_chain_set_emit_tables): 0 automatic, 1 off, 2 on wherever a
+// table fits (both classes' half_bits <= kEmTabMaxHB)
+static int g_emit_tables = 0;
+
+static uint32_t em_half_bits(int64_t N) { return make_feistel(N > 1 ? N : 1, 0).half_bits; }
+static bool em_tables_fit(int64_t NX, int64_t NZ) {
+  return em_half_bits(NX) <= kEmTabMaxHB && em_half_bits(NZ) <= kEmTabMaxHB;
+}
+// entries per (step, class) slot: the larger class's table, padded to whole 16-B loads
+static uint32_t em_tab_stride(int64_t NX, int64_t NZ) {
+  return ((6u << std::max(em_half_bits(NX), em_half_bits(NZ))) + 7u) & ~7u;
+}
+// the launch plan: elements per thread and steps per round (tw_chain_set_emit or automatic)
+// (profiles/r04_chain_parts.log: 2e6 elements, 20 steps: EPR 8 / 1 step per round 257 us,
+// 8 / 2 296 us; 250k elements: 2 / 8 57 us, 2 / 1 79 us, 8 / 1 139 us)
+// (round 5, profiles/r05s46_emit_sweep_ranks.log: a G = 4 rank's 500k elements, 4 per
+// thread and 4 steps per round: 30 against 36 us at K = 4, 92 against 100 at K = 20)
+static void em_plan(int64_t elems, int NB, int& epr, int& spr) {
+  epr = g_emit_epr ? g_emit_epr : elems >= 1500000 ? 8 : elems >= 400000 ? 4 : 2;
+  spr = g_emit_s ? g_emit_s : epr == 8 ? 1 : 16 / epr;
+  while (spr > 1 && spr * NB > kEmMaxB) spr >>= 1;
+}
+// Whether a launch looks its rounds up.  Automatic (tools/emit_tables_ab.py, profiles/
+// r15_emit_tables_ab.json): only one process with strict ties (the slim staging),
+// 8 elements per thread, one step per round and half_bits <= 10 — 0.85 of the arithmetic
+// rounds at 2e6 elements x 20 steps; every other form measured lost (the table's LDS costs the
+// full staging a resident block, several steps per round pay two barriers per step) or was
+// not measured (half_bits 11 in the slim form: 24 KB, three blocks per CU) and stays off.
+static bool em_tables_on(int64_t NX, int64_t NZ, bool full, int epr, int spr) {
+  if (g_emit_tables == 1 || !em_tables_fit(NX, NZ)) return false;
+  if (g_emit_tables == 2) return true;
+  return !full && epr == 8 && spr == 1 && em_half_bits(NX) <= 10 && em_half_bits(NZ) <= 10;
+}
+// the same for a launch by its arguments (chain_emit_impl and tw_chain_emit_tables_of share it)
+static bool em_launch_tables(int64_t n_x, int64_t n_z, int world, bool half, bool xchg,
+                             int n_shards) {
+  const int NB = xchg ? world : n_shards + 1;
+  int epr, spr;
+  em_plan(n_x + n_z, NB, epr, spr);
+  // (the unstaged form, > 512 buckets, was not swept: automatic leaves it as it was)
+  return em_tables_on((int64_t)world * n_x, (int64_t)world * n_z,
+                      xchg || half || NB > kEmMaxB, epr, spr);
+}
+
+static int chain_emit_impl(const uint64_t* d_x_rec, int64_t n_x, const uint64_t* d_z_rec,
+                           int64_t n_z, int32_t half, uint32_t* d_x_pos, uint32_t* d_z_pos,
+                           int32_t first, int32_t rank, int32_t world, const uint64_t* keys_x,
+                           const uint64_t* keys_z, int32_t steps, int64_t x_shard,
+                           int64_t z_shard, int32_t n_shards, void* d_x_bag, void* d_z_bag,
+                           uint32_t* d_cursors, uint64_t* d_send, int64_t cap, int32_t* d_flag,
+                           bool with_work, void* d_work, int64_t work_bytes, void* stream) {
   TW_ARG_CHECK(n_x >= 0 && n_z >= 0 && world >= 1 && rank >= 0 && rank < world &&
                    steps >= 0 && steps <= kChainMax && n_shards >= 0 && x_shard >= 0 &&
                    z_shard >= 0 && (half == 0 || half == 1) && (first == 0 || first == 1),
@@ -1077,23 +1216,61 @@ extern "C" int tw_chain_emit(const uint64_t* d_x_rec, int64_t n_x, const uint64_
   em.send = d_send;
   em.cap = cap;
   em.flag = d_flag;
-  if (xchg) {
-    const int64_t buckets = (int64_t)world * steps;
-    hipLaunchKernelGGL(k_chain_zero_heads, dim3((unsigned)ceil_div(buckets, kBlock)),
-                       dim3(kBlock), 0, st, d_send, buckets, (cap + 1) * em.W);
-  } else {
-    TW_HIP_CHECK(tw_zero_async(d_cursors, 0,
-                               sizeof(unsigned) * (size_t)steps * 2 * (n_shards + 1), st));
+  // the workspace contract holds under every setting of the hook: a caller of the _ws entry
+  // provides tw_chain_emit_work_bytes, checked before anything is launched
+  const int NB = xchg ? world : n_shards + 1;
+  const bool full = xchg || half;
+  int epr, spr;
+  em_plan(n_x + n_z, NB, epr, spr);
+  const bool tabs = with_work && em_launch_tables(n_x, n_z, world, half != 0, xchg, n_shards);
+  if (with_work) {
+    const int64_t need = em_tables_fit(em.NX, em.NZ)
+                             ? (int64_t)steps * 2 * em_tab_stride(em.NX, em.NZ) * 2 : 0;
+    TW_ARG_CHECK(work_bytes >= need && (need == 0 || d_work != nullptr) &&
+                     ((uintptr_t)d_work & 15) == 0,
+                 "tw_chain_emit_ws: workspace of %lld bytes, 16-B aligned, needed",
+                 (long long)need);
+  }
+  em.hbx = em_half_bits(em.NX);
+  em.hbz = em_half_bits(em.NZ);
+  em.tab_stride = tabs ? em_tab_stride(em.NX, em.NZ) : 0;
+  em.tab = tabs ? (const uint16_t*)d_work : nullptr;
+  {
+    // the zeroing and the chunk's tables in one launch
+    ChainRounds rk{};
+    if (tabs)
+      for (int c = 0; c < steps; ++c) {
+        const Feistel fx = make_feistel(em.NX > 1 ? em.NX : 1, keys_x[c]);
+        const Feistel fz = make_feistel(em.NZ > 1 ? em.NZ : 1, keys_z[c]);
+        for (int i = 0; i < 6; ++i) {
+          rk.k[c][0][i] = fx.k[i];
+          rk.k[c][1][i] = fz.k[i];
+        }
+      }
+    const int64_t words = xchg ? (int64_t)world * steps : (int64_t)steps * 2 * (n_shards + 1);
+    const unsigned gy = tabs ? 2u * steps : 1u;
+    const int64_t per = std::max<int64_t>(ceil_div(words, (int64_t)gy),
+                                          tabs ? (int64_t)em.tab_stride : 1);
+    const unsigned gx = (unsigned)std::min<int64_t>(64, ceil_div(per, kBlock));
+    hipLaunchKernelGGL(k_chain_emit_prep, dim3(gx, gy), dim3(kBlock), 0, st,
+                       xchg ? (void*)d_send : (void*)d_cursors, words,
+                       xchg ? (cap + 1) * em.W : (int64_t)0, rk, (uint16_t*)em.tab,
+                       em.tab_stride, em.hbx, em.hbz);
+    TW_LAUNCH_CHECK();
   }
   const ChainKeys k = chain_keys(keys_x, keys_z, steps);
-  const int NB = xchg ? world : n_shards + 1;
-  auto launch = [&](auto epr, auto spr, auto staged) {
-    constexpr int EPR = decltype(epr)::value, S = decltype(spr)::value;
+  const size_t dyn = tabs ? (size_t)em.tab_stride * sizeof(uint16_t) : 0;
+  auto launch = [&](auto epr_c, auto spr_c, auto staged) {
+    constexpr int EPR = decltype(epr_c)::value, S = decltype(spr_c)::value;
     constexpr bool ST = decltype(staged)::value;
     em.bx = (int)ceil_div(n_x, (int64_t)kEmThreads * EPR);
     const int64_t blocks = em.bx + ceil_div(n_z, (int64_t)kEmThreads * EPR);
-    hipLaunchKernelGGL((k_chain_emit<EPR, S, ST>), dim3((unsigned)blocks), dim3(kEmThreads), 0,
-                       st, em, k);
+    if (full)
+      hipLaunchKernelGGL((k_chain_emit<EPR, S, ST, true>), dim3((unsigned)blocks),
+                         dim3(kEmThreads), dyn, st, em, k);
+    else
+      hipLaunchKernelGGL((k_chain_emit<EPR, S, ST, false>), dim3((unsigned)blocks),
+                         dim3(kEmThreads), dyn, st, em, k);
   };
   using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>;
@@ -1101,14 +1278,6 @@ extern "C" int tw_chain_emit(const uint64_t* d_x_rec, int64_t n_x, const uint64_
   using I8 = std::integral_constant<int, 8>;
   using T_ = std::true_type;
   using F_ = std::false_type;
-  // (profiles/r04_chain_parts.log: 2e6 elements, 20 steps: EPR 8 / 1 step per round 257 us,
-  // 8 / 2 296 us; 250k elements: 2 / 8 57 us, 2 / 1 79 us, 8 / 1 139 us)
-  const int64_t elems = n_x + n_z;
-  // (round 5, profiles/r05s46_emit_sweep_ranks.log: a G = 4 rank's 500k elements, 4 per
-  // thread and 4 steps per round: 30 against 36 us at K = 4, 92 against 100 at K = 20)
-  const int epr = g_emit_epr ? g_emit_epr : elems >= 1500000 ? 8 : elems >= 400000 ? 4 : 2;
-  int spr = g_emit_s ? g_emit_s : epr == 8 ? 1 : 16 / epr;
-  while (spr > 1 && spr * NB > kEmMaxB) spr >>= 1;
   if (NB > kEmMaxB) {
     if (epr == 8) launch(I8(), I1(), F_());
     else if (epr == 4) launch(I4(), I1(), F_());
@@ -1125,6 +1294,59 @@ extern "C" int tw_chain_emit(const uint64_t* d_x_rec, int64_t n_x, const uint64_
   }
   TW_LAUNCH_CHECK();
   return TW_OK;
+}
+
+extern "C" int tw_chain_emit(const uint64_t* d_x_rec, int64_t n_x, const uint64_t* d_z_rec,
+                             int64_t n_z, int32_t half, uint32_t* d_x_pos, uint32_t* d_z_pos,
+                             int32_t first, int32_t rank, int32_t world, const uint64_t* keys_x,
+                             const uint64_t* keys_z, int32_t steps, int64_t x_shard,
+                             int64_t z_shard, int32_t n_shards, void* d_x_bag, void* d_z_bag,
+                             uint32_t* d_cursors, uint64_t* d_send, int64_t cap,
+                             int32_t* d_flag, void* stream) {
+  return chain_emit_impl(d_x_rec, n_x, d_z_rec, n_z, half, d_x_pos, d_z_pos, first, rank, world,
+                         keys_x, keys_z, steps, x_shard, z_shard, n_shards, d_x_bag, d_z_bag,
+                         d_cursors, d_send, cap, d_flag, false, nullptr, 0, stream);
+}
+
+// tw_chain_emit with a workspace for the chunk's round tables (the caller's memory, as the
+// planes workspace: written and read inside this one call on this one stream)
+extern "C" int tw_chain_emit_ws(const uint64_t* d_x_rec, int64_t n_x, const uint64_t* d_z_rec,
+                                int64_t n_z, int32_t half, uint32_t* d_x_pos, uint32_t* d_z_pos,
+                                int32_t first, int32_t rank, int32_t world,
+                                const uint64_t* keys_x, const uint64_t* keys_z, int32_t steps,
+                                int64_t x_shard, int64_t z_shard, int32_t n_shards,
+                                void* d_x_bag, void* d_z_bag, uint32_t* d_cursors,
+                                uint64_t* d_send, int64_t cap, int32_t* d_flag, void* d_work,
+                                int64_t work_bytes, void* stream) {
+  return chain_emit_impl(d_x_rec, n_x, d_z_rec, n_z, half, d_x_pos, d_z_pos, first, rank, world,
+                         keys_x, keys_z, steps, x_shard, z_shard, n_shards, d_x_bag, d_z_bag,
+                         d_cursors, d_send, cap, d_flag, true, d_work, work_bytes, stream);
+}
+
+// bytes of tw_chain_emit_ws's workspace for `steps` steps over global sizes (NX, NZ); 0 where
+// no table fits (the launch runs the arithmetic rounds)
+extern "C" int64_t tw_chain_emit_work_bytes(int32_t steps, int64_t NX, int64_t NZ) {
+  if (steps <= 0 || NX < 0 || NZ < 0 || !em_tables_fit(NX, NZ)) return 0;
+  return (int64_t)steps * 2 * em_tab_stride(NX, NZ) * (int64_t)sizeof(uint16_t);
+}
+
+extern "C" int32_t tw_chain_set_emit_tables(int32_t mode) {
+  const int32_t before = g_emit_tables;
+  if (mode == -1) return before;
+  TW_ARG_CHECK(mode >= 0 && mode <= 2,
+               "tw_chain_set_emit_tables: 0 (automatic), 1 (off), 2 (on where a table fits) or -1 "
+               "(report)");
+  g_emit_tables = mode;
+  return before;
+}
+
+// whether the tw_chain_emit_ws launch with these arguments (exchange: a send buffer is given)
+// looks its rounds up under the current settings (this hook and tw_chain_set_emit): the
+// launch's own decision
+extern "C" int32_t tw_chain_emit_tables_of(int64_t n_x, int64_t n_z, int32_t world,
+                                           int32_t half, int32_t exchange, int32_t n_shards) {
+  if (n_x < 0 || n_z < 0 || world < 1 || n_shards < 0) return 0;
+  return em_launch_tables(n_x, n_z, world, half != 0, exchange != 0, n_shards) ? 1 : 0;
 }
 
 extern "C" int tw_chain_set_emit(int32_t epr, int32_t steps_per_round) {

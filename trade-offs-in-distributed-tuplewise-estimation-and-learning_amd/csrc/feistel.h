@@ -2,8 +2,16 @@
 // (csrc/permute.hip; restated in oracle/oracle.py feistel_perm / feistel_perm_inv): a 6-round
 // balanced Feistel network on the smallest even-bit power-of-two domain >= n, cycle-walked
 // into [0, n).
+// Everything but the device-only 32-bit forms is plain C++ (host and device), so
+// tests/native/feisteltab_driver.cpp checks the round tables without a GPU.
 #pragma once
+#if defined(__HIPCC__)
 #include "tw_common.h"
+#define TW_FEISTEL_HD __host__ __device__ inline
+#else
+#include <stdint.h>
+#define TW_FEISTEL_HD inline
+#endif
 
 namespace tw {
 
@@ -16,9 +24,9 @@ struct FastDiv {
   double inv;
 };
 
-__host__ __device__ inline FastDiv make_fastdiv(uint64_t d) { return FastDiv{d, 1.0 / (double)d}; }
+TW_FEISTEL_HD FastDiv make_fastdiv(uint64_t d) { return FastDiv{d, 1.0 / (double)d}; }
 
-__host__ __device__ inline uint64_t fast_div(uint64_t v, const FastDiv& f) {
+TW_FEISTEL_HD uint64_t fast_div(uint64_t v, const FastDiv& f) {
   uint64_t q = (uint64_t)((double)v * f.inv);
   while (q * f.d > v) --q;            // the product is within one of v / d for v < 2^53
   while ((q + 1) * f.d <= v) ++q;
@@ -31,7 +39,7 @@ struct Feistel {
   uint32_t k[6];
 };
 
-__host__ __device__ inline uint32_t mix32(uint32_t v) {  // murmur3 finaliser
+TW_FEISTEL_HD uint32_t mix32(uint32_t v) {  // murmur3 finaliser
   v ^= v >> 16;
   v *= 0x85EBCA6Bu;
   v ^= v >> 13;
@@ -40,7 +48,7 @@ __host__ __device__ inline uint32_t mix32(uint32_t v) {  // murmur3 finaliser
   return v;
 }
 
-__host__ __device__ inline Feistel make_feistel(int64_t n, uint64_t key) {
+TW_FEISTEL_HD Feistel make_feistel(int64_t n, uint64_t key) {
   Feistel f;
   int bits = 2;
   while (bits < 62 && (1ll << bits) < n) ++bits;
@@ -59,7 +67,7 @@ __host__ __device__ inline Feistel make_feistel(int64_t n, uint64_t key) {
   return f;
 }
 
-__host__ __device__ inline uint64_t feistel_once(const Feistel& f, uint64_t v) {
+TW_FEISTEL_HD uint64_t feistel_once(const Feistel& f, uint64_t v) {
   uint32_t L = (uint32_t)(v >> f.half_bits) & f.mask;
   uint32_t R = (uint32_t)v & f.mask;
 #pragma unroll
@@ -71,7 +79,7 @@ __host__ __device__ inline uint64_t feistel_once(const Feistel& f, uint64_t v) {
   return ((uint64_t)L << f.half_bits) | R;
 }
 
-__host__ __device__ inline uint64_t feistel_perm(const Feistel& f, uint64_t i, uint64_t n) {
+TW_FEISTEL_HD uint64_t feistel_perm(const Feistel& f, uint64_t i, uint64_t n) {
   uint64_t v = feistel_once(f, i);
   while (v >= n) v = feistel_once(f, v);  // cycle walking: terminates (bijection on domain)
   return v;
@@ -80,7 +88,7 @@ __host__ __device__ inline uint64_t feistel_perm(const Feistel& f, uint64_t i, u
 // Inverse network: rounds in reverse order.  Round i maps (L, R) -> (R, L ^ F_i(R)), so its
 // inverse maps (L', R') -> (R' ^ F_i(L'), L').  Cycle walking backwards from a position in
 // [0, n) retraces the forward walk, so feistel_perm_inv(feistel_perm(i)) == i.
-__host__ __device__ inline uint64_t feistel_once_inv(const Feistel& f, uint64_t v) {
+TW_FEISTEL_HD uint64_t feistel_once_inv(const Feistel& f, uint64_t v) {
   uint32_t L = (uint32_t)(v >> f.half_bits) & f.mask;
   uint32_t R = (uint32_t)v & f.mask;
 #pragma unroll
@@ -92,7 +100,7 @@ __host__ __device__ inline uint64_t feistel_once_inv(const Feistel& f, uint64_t 
   return ((uint64_t)L << f.half_bits) | R;
 }
 
-__host__ __device__ inline uint64_t feistel_perm_inv(const Feistel& f, uint64_t p, uint64_t n) {
+TW_FEISTEL_HD uint64_t feistel_perm_inv(const Feistel& f, uint64_t p, uint64_t n) {
   uint64_t v = feistel_once_inv(f, p);
   while (v >= n) v = feistel_once_inv(f, v);
   return v;
@@ -100,6 +108,7 @@ __host__ __device__ inline uint64_t feistel_perm_inv(const Feistel& f, uint64_t 
 
 // The same rounds on 32-bit words, for domains of at most 2^32 (half_bits <= 16): the step
 // chains (csrc/chain.hip) keep positions in u32 and evaluate these per element and step.
+#if defined(__HIPCC__)
 __device__ __forceinline__ uint32_t feistel_once32(const Feistel& f, uint32_t v) {
   uint32_t L = (v >> f.half_bits) & f.mask;
   uint32_t R = v & f.mask;
@@ -122,14 +131,51 @@ __device__ __forceinline__ uint32_t feistel_once_inv32(const Feistel& f, uint32_
   }
   return (L << f.half_bits) | R;
 }
+#endif  // __HIPCC__
+
+// Round tables.  The round function F_i(R) = mix32(R * 0x9E3779B1 + k_i) & mask has only
+// 2^half_bits arguments, so for small domains (the step chains' emission, half_bits <=
+// kEmTabMaxHB) all six rounds fit a table of 6 << half_bits 16-bit entries,
+// out[(i << half_bits) + R] = F_i(R): the network then costs one lookup and one xor per round
+// and no multiply.  Every entry is <= mask, so (i << half_bits) + R with R = L ^ entry never
+// leaves the table.  The same permutation bit for bit: the table holds exactly F_i's values.
+constexpr uint32_t kEmTabMaxHB = 11;  // domains up to 2^22: 24 KB per table
+
+// F(R) under round key k (mask < 2^16: an entry fits 16 bits)
+TW_FEISTEL_HD uint16_t feistel_round_value(uint32_t R, uint32_t k, uint32_t mask) {
+  return (uint16_t)(mix32(R * 0x9E3779B1u + k) & mask);
+}
+
+// all 6 << half_bits entries (half_bits <= 16)
+TW_FEISTEL_HD void feistel_round_table(const Feistel& f, uint16_t* out) {
+  for (uint32_t i = 0; i < 6; ++i)
+    for (uint32_t R = 0; R <= f.mask; ++R)
+      out[(i << f.half_bits) + R] = feistel_round_value(R, f.k[i], f.mask);
+}
+
+// feistel_once32 on a round table (half_bits <= 16)
+TW_FEISTEL_HD uint32_t feistel_once32_tab(const uint16_t* tab, uint32_t half_bits, uint32_t mask,
+                                          uint32_t v) {
+  uint32_t L = (v >> half_bits) & mask;
+  uint32_t R = v & mask;
+#pragma unroll
+  for (uint32_t i = 0; i < 6; ++i) {
+    const uint32_t nL = R;
+    R = L ^ tab[(i << half_bits) + R];
+    L = nL;
+  }
+  return (L << half_bits) | R;
+}
 
 // v / d for v < 2^32, d < 2^32: one f64 multiply by the reciprocal (within one of the quotient)
 // and one exact correction each way
+#if defined(__HIPCC__)
 __device__ __forceinline__ uint32_t fast_div32(uint32_t v, const FastDiv& f) {
   uint32_t q = (uint32_t)((double)v * f.inv);
   if ((uint64_t)q * f.d > v) --q;
   else if ((uint64_t)(q + 1) * f.d <= v) ++q;
   return q;
 }
+#endif
 
 }  // namespace tw

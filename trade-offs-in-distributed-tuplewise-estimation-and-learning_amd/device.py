@@ -233,14 +233,43 @@ class HipOps:
     def chain_emit(self, xr, zr, half, xpos, zpos, first, rank, world, keys_x, keys_z, kx, kz,
                    n_shards, x_bag=None, z_bag=None, cursors=None, send=None, cap=0, flag=None):
         """Walk len(keys_x) repartitions for this rank's elements (tw_chain_emit): into the
-        step bags (one process) or the send buckets (several ranks)."""
+        step bags (one process) or the send buckets (several ranks).  The chunk's round tables
+        (tw_chain_emit_ws) live in a workspace of this stream (_emit_work)."""
         kxa = np.ascontiguousarray(keys_x, dtype=np.uint64)
         kza = np.ascontiguousarray(keys_z, dtype=np.uint64)
-        L.call("tw_chain_emit", L.ptr(xr), int(xr.numel()), L.ptr(zr), int(zr.numel()),
+        st = L.stream_handle()
+        work, wb = self._emit_work(len(kxa), int(world) * int(xr.numel()),
+                                   int(world) * int(zr.numel()), st, xr.device)
+        L.call("tw_chain_emit_ws", L.ptr(xr), int(xr.numel()), L.ptr(zr), int(zr.numel()),
                int(bool(half)), L.ptr(xpos), L.ptr(zpos), int(bool(first)), int(rank),
                int(world), kxa.ctypes.data, kza.ctypes.data, len(kxa), int(kx), int(kz),
                int(n_shards), L.ptr(x_bag), L.ptr(z_bag), L.ptr(cursors), L.ptr(send),
-               int(cap), L.ptr(flag), L.stream_handle())
+               int(cap), L.ptr(flag), L.ptr(work), wb, st)
+
+    def _emit_work(self, steps, NX, NZ, st, dev):
+        """The round-table workspace of an emission issued on stream `st` (a raw handle) and
+        its size in bytes (0: no table fits, no buffer).  The contract is _planes_work's: the
+        tables are written and read inside ONE native call on ONE stream, so emissions on one
+        stream reuse the buffer in stream order and emissions on different streams get their
+        own — one per (device, stream handle), grown as needed and never inside a graph
+        capture (run the call once eagerly first)."""
+        sizes = self.__dict__.setdefault("_emit_sizes", {})  # (host time: one lookup per call)
+        wb = sizes.get((steps, NX, NZ))
+        if wb is None:
+            wb = sizes[steps, NX, NZ] = int(
+                L.lib().tw_chain_emit_work_bytes(int(steps), int(NX), int(NZ)))
+        if wb == 0:
+            return None, 0
+        pool = self.__dict__.setdefault("_emit_pool", {})
+        key = (dev.index, st.value)
+        w = pool.get(key)
+        if w is None or w.numel() < wb:
+            if self.t.cuda.is_current_stream_capturing():
+                raise RuntimeError("tuplewise: the emission's table workspace must exist before "
+                                   "a graph capture (run the call once eagerly first)")
+            pool[key] = None  # release the smaller one first
+            pool[key] = w = self.t.empty((max(wb, 4096),), dtype=self.t.uint8, device=dev)
+        return w, wb
 
     def chain_unpack(self, recv, world, steps, cap, half, n, m, x_bag, z_bag, flag, kx, kz,
                      n_shards):
