@@ -1300,6 +1300,58 @@ int tw_triplet_project(const double* d_a, int64_t rows, int32_t d, const double*
 int tw_triplet_sgd_update(const double* d_G, double* d_L, double* d_delta, int32_t count,
                           double reg, double lr, int32_t momentum, void* stream);
 
+/* ---- Kernel two-sample U-statistics of degree (2,2) (csrc/mmd.hip; tuplewise.mmd; DESIGN.md
+ * §4.12; an extension, not in the reference): the unbiased squared maximum mean discrepancy and
+ * the energy distance, both the mean over quadruples of
+ *   h((x, x'), (z, z')) = g(x, x') + g(z, z') - g(x, z') - g(x', z)
+ * d_x is (rows, d) and d_z (rows, d) float64, row-major, 1 <= d <= 64.  D(a, b) is the squared
+ * Euclidean distance of the triplet section, in the same arithmetic order and by the same device
+ * functions (csrc/tripdist.h): acc = 0.0; for c = 0 .. d-1: t = a_c - b_c; acc = acc + t * t,
+ * multiply and add separate, direct differences only — so D(a, a) = 0 exactly and D(a, b) =
+ * D(b, a) bit for bit.  The pair function g:
+ *   TW_MMD_GAUSSIAN  g = exp(fl(c * D)), the float64 exp of the device library; c = -1 / (2
+ *                    sigma^2) is computed by the caller and must be finite and <= 0
+ *   TW_MMD_ENERGY    g = sqrt(D), the correctly rounded float64 square root; c is ignored
+ *
+ * tw_mmd_sums reduces on the device: the partition is given as tw_triplet_rows takes it (block b
+ * owns rows [d_blk_x_off[b], d_blk_x_off[b + 1]) of d_x and [d_blk_z_off[b], d_blk_z_off[b + 1])
+ * of d_z, absolute offsets, n_blocks + 1 entries each; max_n / max_m bound the blocks' sizes),
+ * blocks of any mix of sizes share one launch, and for every block three doubles are written:
+ *   d_out[3 b + 0] = Sxx = sum over i < j of g(x_i, x_j)
+ *   d_out[3 b + 1] = Szz = sum over k < l of g(z_k, z_l)
+ *   d_out[3 b + 2] = Sxz = sum over all (i, k) of g(x_i, z_k)
+ * each unordered pair visited once (the triangles of tile pairs, tw_mmd_tile() rows per tile
+ * edge, and the rectangle of X tiles by Z tiles); a block of fewer than 2 rows of a sample has a
+ * zero sum there.  The statistic is the caller's: V = 2 Sxx / (n (n - 1)) + 2 Szz / (m (m - 1)) -
+ * 2 Sxz / (n m), MMD^2_u = V for the Gaussian kernel and the energy distance = -V.
+ *
+ * tw_mmd_idx32 evaluates given quadruples: for p in [d_quad_off[s], d_quad_off[s + 1]), rows
+ * d_i[p], d_j[p] of d_x and d_k[p], d_l[p] of d_z (absolute, int32), four doubles per shard:
+ *   d_out[4 s + 0] = sum g(x_i, x_j)    d_out[4 s + 1] = sum g(z_k, z_l)
+ *   d_out[4 s + 2] = sum g(x_i, z_l)    d_out[4 s + 3] = sum g(x_j, z_k)
+ * an empty shard gives zeros.
+ *
+ * The sums carry no bit contract (floats added in the kernel's order), but they are run-to-run
+ * deterministic and a block's (shard's) doubles are the same bits alone in a launch or beside
+ * others: no atomics, one partial per workgroup in d_work (tw_mmd_work_bytes /
+ * tw_mmd_idx_work_bytes bytes, nothing to zero), added in a fixed order as tw_self_pairs'.  A NaN
+ * coordinate makes every sum it enters NaN; infinities follow IEEE arithmetic.
+ *
+ * Argument errors (a null pointer, d outside [1, 64], a negative size, an unknown kernel id, a
+ * non-finite or positive c for the Gaussian kernel) return TW_ERR_ARG before any device work. */
+#define TW_MMD_GAUSSIAN 0
+#define TW_MMD_ENERGY 1
+int32_t tw_mmd_tile(void);
+int64_t tw_mmd_work_bytes(int32_t n_blocks, int64_t max_n, int64_t max_m);
+int64_t tw_mmd_idx_work_bytes(int32_t n_shards, int64_t max_quads);
+int tw_mmd_sums(const double* d_x, const double* d_z, int32_t d, const int64_t* d_blk_x_off,
+                const int64_t* d_blk_z_off, int32_t n_blocks, int64_t max_n, int64_t max_m,
+                int32_t kern, double c, void* d_work, double* d_out, void* stream);
+int tw_mmd_idx32(const double* d_x, const double* d_z, int32_t d, const int32_t* d_i,
+                 const int32_t* d_j, const int32_t* d_k, const int32_t* d_l,
+                 const int64_t* d_quad_off, int32_t n_shards, int64_t max_quads, int32_t kern,
+                 double c, void* d_work, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,16 +35,6 @@ inline int64_t self_idx_blocks_per_shard(int64_t max_pairs) {
   return std::max<int64_t>(1, ceil_div(max_pairs, (int64_t)kBlock * kSelfPPT));
 }
 
-// Triangle index p = J (J + 1) / 2 + I, I <= J, back to (I, J): the double root is exact
-// enough to land within one of J for every p < 2^52, the two loops settle it.
-__device__ __forceinline__ void self_tile_of(int64_t p, int& I, int& J) {
-  int64_t j = (int64_t)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-  while (j * (j + 1) / 2 > p) --j;
-  while ((j + 1) * (j + 2) / 2 <= p) ++j;
-  J = (int)j;
-  I = (int)(p - j * (j + 1) / 2);
-}
-
 // One Kendall point: the LDS tile holds them as 16-byte items (one ds_read_b128 per j,
 // broadcast to the wave).
 template <typename V>

@@ -9,39 +9,13 @@
 // anchor one shard.  tw_triplet_idx32 evaluates given triplets (i, j, k) directly.
 #include "tw_common.h"
 #include "selfreduce.h"
+#include "tripdist.h"
 #include <algorithm>
 
 namespace tw {
 
-constexpr int kTripMaxD = 64;                 // coordinates per row, at most
-constexpr int kTripTA = 16;                   // anchors per tile (feature rows staged in LDS)
-constexpr int kTripR = 2;                     // points per lane
 constexpr int kTripP = kBlock * kTripR;       // points per tile edge
-constexpr int kTripDC = 8;                    // coordinates of a lane's points held in registers
 constexpr int kTripPPT = 4;                   // triplets per lane (tw_triplet_idx32)
-
-// One chunk of coordinates [c0, c0 + kTripDC) of this lane's points against every anchor of the
-// tile: the anchor's coordinate is one wave-uniform LDS read (a broadcast), used for kTripR
-// points.  TAIL: the chunk runs past d (block-uniform tests, no lane diverges).
-template <bool TAIL>
-__device__ __forceinline__ void trip_chunk(const double* __restrict__ sa, int c0, int d,
-                                           const double (&pc)[kTripR][kTripDC],
-                                           double (&acc)[kTripTA][kTripR]) {
-#pragma unroll
-  for (int a = 0; a < kTripTA; ++a) {
-#pragma unroll
-    for (int c = 0; c < kTripDC; ++c) {
-      if (!TAIL || c0 + c < d) {
-        const double s = sa[a * kTripMaxD + c0 + c];
-#pragma unroll
-        for (int r = 0; r < kTripR; ++r) {
-          const double t = s - pc[r][c];
-          acc[a][r] = acc[a][r] + t * t;
-        }
-      }
-    }
-  }
-}
 
 // A NaN distance is stored as THE quiet NaN 0x7ff8000000000000: which NaN an operation returns
 // (sign, payload) is the hardware's choice — a subtraction here negates its NaN operand, an x86
@@ -139,18 +113,6 @@ __global__ __launch_bounds__(kBlock) void k_triplet_rows(
       }
     }
   }
-}
-
-// D(a, b) over d coordinates in the contract's order.
-__device__ __forceinline__ double trip_dist(const double* __restrict__ a,
-                                            const double* __restrict__ b, int d) {
-  double acc = 0.0;
-#pragma unroll 4
-  for (int c = 0; c < d; ++c) {
-    const double t = a[c] - b[c];
-    acc = acc + t * t;
-  }
-  return acc;
 }
 
 // The given triplets of every shard's range: absolute rows i, j of x and k of z.

@@ -1,0 +1,287 @@
+"""Kernel two-sample U-statistics of degree (2,2) on MI355X (an extension; the reference has
+none): the unbiased squared maximum mean discrepancy MMD^2_u (Gretton et al.) and the energy
+distance (Szekely-Rizzo), both the mean over quadruples of
+
+    h((x, x'), (z, z')) = g(x, x') + g(z, z') - g(x, z') - g(x', z)
+
+X is (n, d) and Z is (m, d), float64 and C-contiguous (a 1-D array is d = 1), 1 <= d <= 64,
+n >= 2, m >= 2; anything else is a ValueError before any device work or RNG draw.
+
+D(a, b) is the squared Euclidean distance of tuplewise.triplets, in its arithmetic order (acc =
+0.0; for c in 0..d-1: t = a_c - b_c; acc = acc + t * t, never fused, direct differences only), so
+D(a, a) = 0 exactly and D(a, b) = D(b, a) bit for bit.  The pair function:
+
+    kernel="gaussian"  g = exp(c * D), c = -1.0 / (2.0 * sigma * sigma) computed here in Python
+                       floats; sigma is required, positive and finite
+    kernel="energy"    g = sqrt(D); sigma must be None
+
+The device reduces (csrc/mmd.hip): per block three doubles leave the chip,
+
+    Sxx = sum_{i<j} g(x_i, x_j)    Szz = sum_{k<l} g(z_k, z_l)    Sxz = sum_{i,k} g(x_i, z_k)
+
+and the statistic is formed here: V = 2 Sxx / (n (n - 1)) + 2 Szz / (m (m - 1)) - 2 Sxz / (n m);
+the Gaussian value is V (MMD^2_u), the energy value is -V (the energy distance is MMD^2_u with
+k = -|.|).  The sums are floats added in the kernel's order: no bit contract, but run-to-run
+deterministic, and a block's sums are the same bits alone or beside other blocks.  The
+incomplete statistic evaluates h on drawn quadruples (i != j rows of X, k != l rows of Z) through
+tw_mmd_idx32.  The estimators mirror tuplewise.triplets for the proportional partition without
+replacement: the host owns the shuffles and the draws (NumPy's global legacy RNG, in NumPy's
+order), the device the arithmetic.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _lib as L
+from .compute_stats import _check_index
+from .numpy_rng import randint_batch
+from .triplets import _rows
+
+_KERNELS = {"gaussian": L.TW_MMD_GAUSSIAN, "energy": L.TW_MMD_ENERGY}
+MAX_D = 64
+
+
+# ------------------------------------------------------------------------------ host checks
+def _coef(kernel, sigma):
+    """(kernel id, c) or a ValueError: c = -1 / (2 sigma^2) for the Gaussian kernel, 0.0 (unused)
+    for the energy kernel."""
+    if kernel not in _KERNELS:
+        raise ValueError(f"kernel={kernel!r} is not one of {list(_KERNELS)}")
+    if kernel == "energy":
+        if sigma is not None:
+            raise ValueError("the energy kernel takes no sigma")
+        return _KERNELS[kernel], 0.0
+    if sigma is None:
+        raise ValueError("the Gaussian kernel needs sigma")
+    try:
+        sigma = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"sigma={sigma!r} is not a number") from None
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f"sigma = {sigma} must be positive and finite")
+    if 2.0 * sigma * sigma == 0.0:
+        raise ValueError(f"sigma = {sigma}: -1 / (2 sigma^2) overflows")
+    return _KERNELS[kernel], -1.0 / (2.0 * sigma * sigma)
+
+
+def _check(X, Z, kernel, sigma):
+    """(Xf, Zf, kernel id, c) or a ValueError, before anything touches a device or the RNG."""
+    kid, c = _coef(kernel, sigma)
+    Xf, Zf = _rows(X, "X"), _rows(Z, "Z")
+    d = Xf.shape[1]
+    if Zf.shape[1] != d:
+        raise ValueError(f"X has {d} coordinates and Z has {Zf.shape[1]}")
+    if not 1 <= d <= MAX_D:
+        raise ValueError(f"d = {d} is outside [1, {MAX_D}]")
+    for A, name in ((Xf, "X"), (Zf, "Z")):
+        if A.shape[0] < 2:
+            raise ValueError(f"{name} has {A.shape[0]} row(s): a quadruple needs two points of "
+                             f"each sample")
+    if max(Xf.shape[0], Zf.shape[0]) >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 rows per sample")
+    return Xf, Zf, kid, c
+
+
+def _value(sxx, szz, sxz, n: int, m: int, kid: int) -> np.float64:
+    v = 2.0 * sxx / (n * (n - 1)) + 2.0 * szz / (m * (m - 1)) - 2.0 * sxz / (n * m)
+    return np.float64(v if kid == L.TW_MMD_GAUSSIAN else -v)
+
+
+def _value_indexed(s, B: int, kid: int) -> np.float64:
+    v = (s[0] + s[1] - s[2] - s[3]) / B
+    return np.float64(v if kid == L.TW_MMD_GAUSSIAN else -v)
+
+
+# ------------------------------------------------------------------------------ device glue
+def _sums_blocks(Xf, Zf, bxo, bzo, kid, c):
+    """tw_mmd_sums on one upload: the (n_blocks, 3) doubles Sxx, Szz, Sxz of the blocks b = rows
+    [bxo[b], bxo[b + 1]) of Xf against rows [bzo[b], bzo[b + 1]) of Zf."""
+    t = L.torch()
+    L.device()  # no HIP device: the package's RuntimeError, before any native call
+    bxo, bzo = np.asarray(bxo, dtype=np.int64), np.asarray(bzo, dtype=np.int64)
+    nb = len(bxo) - 1
+    max_n, max_m = int(np.diff(bxo).max()), int(np.diff(bzo).max())
+    xd, zd, bx, bz = L.to_device_many([Xf.reshape(-1), Zf.reshape(-1), bxo, bzo])
+    work = L.empty((max(1, int(L.lib().tw_mmd_work_bytes(nb, max_n, max_m)) // 8),), t.float64)
+    out = L.empty((nb, 3), t.float64)
+    L.call("tw_mmd_sums", xd, zd, Xf.shape[1], bx, bz, nb, max_n, max_m, kid, c, work, out,
+           L.stream_handle())
+    return out.cpu().numpy()
+
+
+def _sums_indexed(Xf, Zf, ii, jj, kk, ll, quad_off, kid, c):
+    """tw_mmd_idx32 on one upload: the (n_shards, 4) doubles of the given quadruples (absolute
+    rows)."""
+    t = L.torch()
+    L.device()
+    quad_off = np.asarray(quad_off, dtype=np.int64)
+    ns = len(quad_off) - 1
+    xd, zd, id_, jd, kd, ld, od = L.to_device_many(
+        [Xf.reshape(-1), Zf.reshape(-1), ii.astype(np.int32), jj.astype(np.int32),
+         kk.astype(np.int32), ll.astype(np.int32), quad_off])
+    max_q = int(np.diff(quad_off).max()) if ns else 0
+    work = L.empty((max(1, int(L.lib().tw_mmd_idx_work_bytes(ns, max_q)) // 8),), t.float64)
+    out = L.empty((ns, 4), t.float64)
+    L.call("tw_mmd_idx32", xd, zd, Xf.shape[1], id_, jd, kd, ld, od, ns, max_q, kid, c, work, out,
+           L.stream_handle())
+    return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------- estimators
+def components(X, Z, kernel="gaussian", sigma=None):
+    """(Sxx, Szz, Sxz): the three sums of g over the pairs of X, the pairs of Z and all (x, z)."""
+    Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    s = _sums_blocks(Xf, Zf, [0, Xf.shape[0]], [0, Zf.shape[0]], kid, c)[0]
+    return np.float64(s[0]), np.float64(s[1]), np.float64(s[2])
+
+
+def Un(X, Z, kernel="gaussian", sigma=None):
+    """The complete statistic: MMD^2_u (Gaussian) or the energy distance."""
+    Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    sxx, szz, sxz = _sums_blocks(Xf, Zf, [0, Xf.shape[0]], [0, Zf.shape[0]], kid, c)[0]
+    return _value(sxx, szz, sxz, Xf.shape[0], Zf.shape[0], kid)
+
+
+def UB_indices(X, Z, i, j, k, l, kernel="gaussian", sigma=None):  # noqa: E741
+    """The mean of h over the given quadruples ((x_i[p], x_j[p]), (z_k[p], z_l[p])), i[p] != j[p]
+    and k[p] != l[p]."""
+    Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    n, m = Xf.shape[0], Zf.shape[0]
+    i, j = _check_index(np.asarray(i), n), _check_index(np.asarray(j), n)
+    k, l = _check_index(np.asarray(k), m), _check_index(np.asarray(l), m)  # noqa: E741
+    if not i.shape == j.shape == k.shape == l.shape:
+        raise ValueError(f"operands could not be broadcast together with shapes "
+                         f"{i.shape} {j.shape} {k.shape} {l.shape}")
+    i, j, k, l = (a.reshape(-1) for a in (i, j, k, l))  # noqa: E741
+    if np.any(i == j) or np.any(k == l):  # (rows as _check_index returns them, >= 0)
+        raise ValueError("a quadruple needs i != j and k != l")
+    if i.size == 0:
+        return np.float64("nan")  # the mean of no terms
+    s = _sums_indexed(Xf, Zf, i, j, k, l, [0, i.size], kid, c)[0]
+    return _value_indexed(s, i.size, kid)
+
+
+def _pairs_from(a, b):
+    return a, b + (b >= a)
+
+
+def _draw_quadruples(n: int, m: int, B: int):
+    """B quadruples, uniform over i != j and k != l: i = randint(0, n, B); j = randint(0, n - 1,
+    B); j += (j >= i); k = randint(0, m, B); l = randint(0, m - 1, B); l += (l >= k) — from the
+    global legacy RNG, in this order."""
+    try:  # the same four calls (values and state) in one native call
+        i, j, k, l = randint_batch([(0, n, B), (0, n - 1, B), (0, m, B), (0, m - 1, B)])  # noqa: E741
+    except NotImplementedError:  # the global generator is not the legacy MT19937
+        i = np.random.randint(0, n, B)
+        j = np.random.randint(0, n - 1, B)
+        k = np.random.randint(0, m, B)
+        l = np.random.randint(0, m - 1, B)  # noqa: E741
+    return _pairs_from(i, j) + _pairs_from(k, l)
+
+
+def UB(X, Z, B, kernel="gaussian", sigma=None):
+    """The incomplete statistic: B quadruples drawn with replacement."""
+    Xf, Zf, _, _ = _check(X, Z, kernel, sigma)
+    i, j, k, l = _draw_quadruples(Xf.shape[0], Zf.shape[0], int(B))  # noqa: E741
+    return UB_indices(Xf, Zf, i, j, k, l, kernel, sigma)
+
+
+class _Complete:
+    """Tag of a block function made by UnN: every block's Un, all blocks in one tw_mmd_sums
+    launch."""
+
+    def __init__(self, kernel, sigma):
+        self.kid, self.c = _coef(kernel, sigma)
+
+    def evaluate(self, Xf, Zf, k, kz, N):
+        s = _sums_blocks(Xf[:N * k], Zf[:N * kz], np.arange(N + 1) * k, np.arange(N + 1) * kz,
+                         self.kid, self.c)
+        return [_value(b[0], b[1], b[2], k, kz, self.kid) for b in s]
+
+
+class _Incomplete:
+    """Tag of a block function made by UnNB: every block's UB, the draws in block order (i, j,
+    k, l for each block), all blocks in one tw_mmd_idx32 launch."""
+
+    def __init__(self, B, kernel, sigma):
+        self.B = int(B)
+        self.kid, self.c = _coef(kernel, sigma)
+
+    def evaluate(self, Xf, Zf, k, kz, N):
+        B = self.B
+        try:  # the 4N calls of the N blocks, in their order, in one native call
+            d = randint_batch([(0, k, B), (0, k - 1, B), (0, kz, B), (0, kz - 1, B)] * N)
+            draws = [_pairs_from(d[4 * b], d[4 * b + 1]) + _pairs_from(d[4 * b + 2], d[4 * b + 3])
+                     for b in range(N)]
+        except NotImplementedError:  # the global generator is not the legacy MT19937
+            draws = [_draw_quadruples(k, kz, B) for _ in range(N)]
+        if B == 0:
+            return [np.float64("nan")] * N
+        ii = np.concatenate([q[0] + b * k for b, q in enumerate(draws)])
+        jj = np.concatenate([q[1] + b * k for b, q in enumerate(draws)])
+        kk = np.concatenate([q[2] + b * kz for b, q in enumerate(draws)])
+        ll = np.concatenate([q[3] + b * kz for b, q in enumerate(draws)])
+        s = _sums_indexed(Xf[:N * k], Zf[:N * kz], ii, jj, kk, ll, np.arange(N + 1) * B,
+                          self.kid, self.c)
+        return [_value_indexed(b, B, self.kid) for b in s]
+
+
+def _block_fn(spec, fn):
+    fn._tw_mmd_block = spec
+    return fn
+
+
+def UN(X, Z, N, f_block, sampling_type="prop-SWOR"):
+    """Shuffles X, then Z, in place (rows), cuts N blocks of k = int(n / N) rows of X and
+    kz = int(m / N) rows of Z (the remainders are left out) and averages f_block(x, z) over
+    them.  Block functions made by this module (the closures of UnN / UnNB) are evaluated
+    together on the device; any other callable is called block by block."""
+    if sampling_type != "prop-SWOR":
+        raise ValueError(f"sampling_type={sampling_type!r}: only the proportional partition "
+                         f"without replacement ('prop-SWOR') is offered for the MMD; 'SWOR' and "
+                         f"'prop-SWR' are out of scope (DESIGN.md §4.12)")
+    if not isinstance(X, np.ndarray) or not isinstance(Z, np.ndarray):
+        raise ValueError("UN shuffles the caller's NumPy arrays in place")
+    spec = getattr(f_block, "_tw_mmd_block", None)
+    Xf, Zf, _, _ = _check(X, Z, "energy", None)
+    k, kz = int(Xf.shape[0] / N), int(Zf.shape[0] / N)
+    if k < 2 or kz < 2:
+        raise ValueError(f"N = {N} blocks of {k} row(s) of X and {kz} of Z: a block needs at "
+                         f"least 2 rows of each sample")
+    np.random.shuffle(X)
+    np.random.shuffle(Z)
+    if spec is not None:
+        return np.mean(spec.evaluate(Xf, Zf, k, kz, N))  # Xf / Zf view the shuffled arrays
+    return np.mean([f_block(X[b * k:(b + 1) * k], Z[b * kz:(b + 1) * kz]) for b in range(N)])
+
+
+def UnN(X, Z, N, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
+    """Block-wise complete statistic."""
+
+    def fun_block(x, z):
+        return Un(x, z, kernel=kernel, sigma=sigma)
+
+    _check(X, Z, kernel, sigma)
+    return UN(X, Z, N, _block_fn(_Complete(kernel, sigma), fun_block), sampling_type)
+
+
+def UnNB(X, Z, N, B, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
+    """Block-wise incomplete statistic."""
+
+    def fun_block(x, z):
+        return UB(x, z, B, kernel=kernel, sigma=sigma)
+
+    _check(X, Z, kernel, sigma)
+    return UN(X, Z, N, _block_fn(_Incomplete(B, kernel, sigma), fun_block), sampling_type)
+
+
+def UnNT(X, Z, N, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
+    """Reshuffled block-wise complete statistic."""
+    return np.mean([UnN(X, Z, N, sampling_type, kernel, sigma) for _ in range(T)])
+
+
+def UnNBT(X, Z, N, B, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
+    """Reshuffled block-wise incomplete statistic."""
+    return np.mean([UnNB(X, Z, N, B, sampling_type, kernel, sigma) for _ in range(T)])
