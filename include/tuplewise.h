@@ -1352,6 +1352,33 @@ int tw_mmd_idx32(const double* d_x, const double* d_z, int32_t d, const int32_t*
                  const int64_t* d_quad_off, int32_t n_shards, int64_t max_quads, int32_t kern,
                  double c, void* d_work, double* d_out, void* stream);
 
+/* ---- The permutation test of the statistics above (csrc/mmd_perm.hip; tuplewise.mmd
+ * permutation_sums / permutation_test; an extension): Sxx, Szz, Sxz of EVERY
+ * relabelling of the pooled sample in one launch.  d_w is the pooled sample, (n_rows, d) float64
+ * row-major, first sample first; g, kern and c as above.  d_labels[r * W + w], W = ceil(n_perm /
+ * 32) uint32 words a row: bit b is 1 iff row r is in the first sample under permutation
+ * (column) 32 w + b; padding bits are 0.  For every column p
+ *   d_out[3 p + 0] = Sxx_p   d_out[3 p + 1] = Szz_p   d_out[3 p + 2] = Sxz_p
+ * as tw_mmd_sums orders them.  Each g(w_i, w_j), i < j, is evaluated once per pass of
+ * tw_mmd_perm_cols() columns and multiplied by the labels as exact 0.0 / 1.0 on the float64
+ * matrix unit: with s the column's labels, Sxx = sum s_i s_j g_ij, A = sum (s_i + s_j) g_ij,
+ * T = sum g_ij, Sxz = A - 2 Sxx and Szz = T - A + Sxx (Szz and Sxz are differences of sums of
+ * the size of T).  No atomics: one partial per workgroup and column in d_work
+ * (tw_mmd_perm_work_bytes bytes, nothing to zero), added in a fixed order.  Results are run-to-run
+ * deterministic, and a column's three doubles depend only on d_w and on that column's labels —
+ * not on its position p, on n_perm or on the other columns.  A NaN coordinate anywhere makes
+ * every column NaN (0 * NaN).
+ *
+ * TW_ERR_ARG before any device work: a null pointer, d outside [1, 64], n_rows < 4 or >= 2^31,
+ * n_perm < 1 (a test has at least the observed split), an unknown kernel id, a non-finite or
+ * positive c for the Gaussian kernel, a grid past 2^31 workgroups.  tw_mmd_perm_work_bytes is 0
+ * for sizes tw_mmd_perm_sums refuses. */
+int32_t tw_mmd_perm_cols(void);
+int64_t tw_mmd_perm_work_bytes(int64_t n_rows, int32_t n_perm);
+int tw_mmd_perm_sums(const double* d_w, int64_t n_rows, int32_t d, const uint32_t* d_labels,
+                     int32_t n_perm, int32_t kern, double c, void* d_work, double* d_out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

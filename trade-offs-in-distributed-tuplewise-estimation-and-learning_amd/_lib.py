@@ -273,6 +273,9 @@ _SIGNATURES = {
     "tw_mmd_sums": [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _f64, _vp, _vp, _vp],
     "tw_mmd_idx32": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f64, _vp, _vp,
                      _vp],
+    "tw_mmd_perm_cols": [],
+    "tw_mmd_perm_work_bytes": [_i64, _i32],
+    "tw_mmd_perm_sums": [_vp, _i64, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -299,6 +302,7 @@ _RESTYPES = {
     "tw_triplet_grad_work_bytes": ctypes.c_int64,
     "tw_mmd_work_bytes": ctypes.c_int64,
     "tw_mmd_idx_work_bytes": ctypes.c_int64,
+    "tw_mmd_perm_work_bytes": ctypes.c_int64,
 }
 
 _lib = None

@@ -21,16 +21,14 @@
 #include "tw_common.h"
 #include "selfreduce.h"
 #include "tripdist.h"
+#include "mmdtile.h"  // kMmdT, kMmdSA, mmd_g, mmd_load, TW_MMD_KERN_CHECKS (shared with mmd_perm.hip)
 #include <algorithm>
 #include <cmath>
 
 namespace tw {
 
-constexpr int kMmdT = kWave * kTripR;                   // rows per tile edge (points of a lane: r * 64 + lane)
-constexpr int kMmdSA = (kBlock / kWave) * kTripTA;      // anchors staged per step, kTripTA a wave
 constexpr int kMmdG = 2;                                // tile pairs per workgroup
 constexpr int kMmdQPT = 4;                              // quadruples per lane (tw_mmd_idx32)
-static_assert(kMmdT % kMmdSA == 0, "a tile is a whole number of anchor steps");
 
 inline int64_t mmd_tiles(int64_t n) { return ceil_div(n, kMmdT); }
 inline int64_t mmd_items(int64_t n, int64_t m) {
@@ -42,23 +40,6 @@ inline int64_t mmd_blocks_per_block(int64_t max_n, int64_t max_m) {
 }
 inline int64_t mmd_idx_blocks_per_shard(int64_t max_quads) {
   return std::max<int64_t>(1, ceil_div(max_quads, (int64_t)kBlock * kMmdQPT));
-}
-
-template <int K>
-__device__ __forceinline__ double mmd_g(double dist, double c) {
-  if constexpr (K == TW_MMD_GAUSSIAN) return exp(c * dist);
-  else return sqrt(dist);
-}
-
-// Coordinates [c0, c0 + kTripDC) of this lane's points.  TAIL: the chunk runs past d (zeros there).
-template <bool TAIL>
-__device__ __forceinline__ void mmd_load(const double* __restrict__ const (&row)[kTripR], int c0,
-                                         int d, double (&pc)[kTripR][kTripDC]) {
-#pragma unroll
-  for (int r = 0; r < kTripR; ++r)
-#pragma unroll
-    for (int cc = 0; cc < kTripDC; ++cc)
-      pc[r][cc] = (!TAIL || c0 + cc < d) ? row[r][c0 + cc] : 0.0;
 }
 
 // g of the wave's kTripTA x kTripR distances, added in a fixed order.  MASK: anchors past the
@@ -228,12 +209,6 @@ __global__ __launch_bounds__(kBlock) void k_mmd_idx(
 }  // namespace tw
 
 using namespace tw;
-
-#define TW_MMD_KERN_CHECKS(fn)                                                                  \
-  TW_ARG_CHECK(d >= 1 && d <= kTripMaxD, fn ": d %d outside [1, %d]", d, kTripMaxD);            \
-  TW_ARG_CHECK(kern == TW_MMD_GAUSSIAN || kern == TW_MMD_ENERGY, fn ": unknown kernel %d", kern); \
-  TW_ARG_CHECK(kern != TW_MMD_GAUSSIAN || (std::isfinite(c) && c <= 0.0),                       \
-               fn ": c = %g for the Gaussian kernel (finite and <= 0: -1 / (2 sigma^2))", c)
 
 extern "C" int32_t tw_mmd_tile(void) { return kMmdT; }
 

@@ -27,10 +27,18 @@ incomplete statistic evaluates h on drawn quadruples (i != j rows of X, k != l r
 tw_mmd_idx32.  The estimators mirror tuplewise.triplets for the proportional partition without
 replacement: the host owns the shuffles and the draws (NumPy's global legacy RNG, in NumPy's
 order), the device the arithmetic.
+
+The permutation test (permutation_sums, permutation_test; csrc/mmd_perm.hip)
+relabels the pooled sample: every permutation's three sums come from ONE launch that evaluates
+each g(w_i, w_j) once per pass of tw_mmd_perm_cols() permutations and multiplies it by the 0 / 1
+labels on the float64 matrix unit.  A column's sums depend only on the rows and on that column's
+labels, bit for bit, so a permutation that reproduces the observed split compares equal to the
+observed value.  A NaN coordinate anywhere makes every column NaN.
 """
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 
@@ -285,3 +293,84 @@ def UnNT(X, Z, N, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
 def UnNBT(X, Z, N, B, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Reshuffled block-wise incomplete statistic."""
     return np.mean([UnNB(X, Z, N, B, sampling_type, kernel, sigma) for _ in range(T)])
+
+
+# ------------------------------------------------------------------------- permutation test
+class PermutationResult(NamedTuple):
+    """statistic: the observed value; null: the (n_perm,) values under the permutations;
+    pvalue = (1 + #{null >= statistic}) / (1 + n_perm)."""
+    statistic: np.float64
+    null: np.ndarray
+    pvalue: float
+
+
+def _check_labels(labels, n: int, N: int):
+    """labels as a (P, N) bool array with exactly n True a row, P >= 1, or a ValueError."""
+    if not isinstance(labels, np.ndarray) or labels.dtype != np.bool_:
+        raise ValueError("labels must be a NumPy bool array")
+    if labels.ndim != 2 or labels.shape[1] != N or labels.shape[0] < 1:
+        raise ValueError(f"labels has shape {labels.shape}: (P, n + m) = (P >= 1, {N}) expected")
+    if labels.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 permutations")
+    counts = labels.sum(axis=1)
+    if np.any(counts != n):
+        bad = int(np.flatnonzero(counts != n)[0])
+        raise ValueError(f"labels[{bad}] marks {int(counts[bad])} rows, not the n = {n} of X")
+    return labels
+
+
+def _perm_sums(Xf, Zf, labels, kid, c):
+    """tw_mmd_perm_sums on one upload: the (P, 3) doubles Sxx, Szz, Sxz of every row of labels."""
+    t = L.torch()
+    L.device()  # no HIP device: the package's RuntimeError, before any native call
+    P, N = labels.shape
+    # bit b of word w of row r: permutation 32 w + b (little-endian words, zero padding)
+    packed = np.packbits(labels.T, axis=1, bitorder="little")
+    W = (P + 31) // 32
+    words = np.zeros((N, 4 * W), dtype=np.uint8)
+    words[:, :packed.shape[1]] = packed
+    pool = np.concatenate([Xf, Zf]).reshape(-1)
+    wd, ld = L.to_device_many([pool, words.view("<i4").reshape(-1)])
+    work = L.empty((max(1, int(L.lib().tw_mmd_perm_work_bytes(N, P)) // 8),), t.float64)
+    out = L.empty((P, 3), t.float64)
+    L.call("tw_mmd_perm_sums", wd, N, Xf.shape[1], ld, P, kid, c, work, out, L.stream_handle())
+    return out.cpu().numpy()
+
+
+def permutation_sums(X, Z, labels, kernel="gaussian", sigma=None):
+    """The (P, 3) float64 sums (Sxx, Szz, Sxz) of the P relabellings of the pooled sample
+    W = [X; Z]: labels is a (P, n + m) bool array, row p marking the n rows of W that are the
+    first sample under permutation p.  The device path of permutation_test with nothing drawn:
+    one upload and one launch."""
+    Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    labels = _check_labels(labels, Xf.shape[0], Xf.shape[0] + Zf.shape[0])
+    return _perm_sums(Xf, Zf, labels, kid, c)
+
+
+def permutation_test(X, Z, n_perm, kernel="gaussian", sigma=None):
+    """The permutation test of the complete statistic (MMD^2_u or the energy distance): the
+    observed value, its n_perm values under uniform relabellings of the pooled sample and
+    pvalue = (1 + #{null >= statistic}) / (1 + n_perm).
+
+    Permutation p = 1 .. n_perm is pi = np.random.permutation(n + m) on NumPy's global legacy
+    RNG, drawn in this order; its first sample is rows pi[:n] of the pool [X; Z].  X and Z are not
+    modified.  The observed split is column 0 of the same launch, so `statistic` may differ from
+    Un(X, Z) in the last bits (a different order of summation), while a permutation that
+    reproduces the observed split gives exactly `statistic`."""
+    if isinstance(n_perm, bool) or not isinstance(n_perm, (int, np.integer)) or n_perm < 1:
+        raise ValueError(f"n_perm = {n_perm!r} must be an int >= 1")
+    n_perm = int(n_perm)
+    if n_perm >= 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 2 permutations")
+    Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    L.device()  # no HIP device: the package's RuntimeError, before any draw
+    n, m = Xf.shape[0], Zf.shape[0]
+    labels = np.zeros((n_perm + 1, n + m), dtype=np.bool_)
+    labels[0, :n] = True
+    for p in range(1, n_perm + 1):
+        labels[p, np.random.permutation(n + m)[:n]] = True
+    s = _perm_sums(Xf, Zf, labels, kid, c)
+    values = np.asarray(_value(s[:, 0], s[:, 1], s[:, 2], n, m, kid), dtype=np.float64)
+    statistic, null = np.float64(values[0]), values[1:].copy()
+    return PermutationResult(statistic, null,
+                             (1 + int(np.count_nonzero(null >= statistic))) / (1 + n_perm))
