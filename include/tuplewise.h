@@ -1379,6 +1379,71 @@ int tw_mmd_perm_sums(const double* d_w, int64_t n_rows, int32_t d, const uint32_
                      int32_t n_perm, int32_t kern, double c, void* d_work, double* d_out,
                      void* stream);
 
+/* ---- Kernel independence U-statistics of degree 4 on one paired sample (csrc/hsic.hip;
+ * tuplewise.hsic; an extension): the unbiased Hilbert-Schmidt independence
+ * criterion HSIC_u (Song et al. 2012) and the unbiased squared distance covariance
+ * (Szekely-Rizzo 2014), with what their normalised forms need.  d_x is (rows, dx) and d_y
+ * (rows, dy) float64, row-major, 1 <= dx, dy <= 64; row i of d_x and row i of d_y are one item.
+ * D is the squared distance of the triplet section (csrc/tripdist.h) and g the pair function of
+ * the MMD section (the same device functions, so a K_ij has the bits tw_mmd_sums gives it):
+ *   K_ij = g(D(x_i, x_j); c_x)   L_ij = g(D(y_i, y_j); c_y)   zero diagonals
+ *   TW_HSIC_GAUSSIAN  g = exp(fl(c * D)), c = -1 / (2 sigma^2) per side, finite and <= 0
+ *   TW_HSIC_DISTANCE  g = sqrt(D); c_x, c_y are ignored
+ * and the row sums k_i = sum over j != i of K_ij, l_i likewise.
+ *
+ * tw_hsic_sums: block b is rows [d_blk_off[b], d_blk_off[b + 1]) of BOTH arrays (absolute
+ * offsets, n_blocks + 1 entries; max_n bounds the blocks' sizes and must be >= 4).  Blocks of any
+ * mix of sizes share one launch, and for every block eight doubles are written:
+ *   d_out[8 b + 0] = S_KL = sum over i < j of K_ij L_ij     d_out[8 b + 3] = R_K  = sum_i k_i
+ *   d_out[8 b + 1] = S_KK = sum over i < j of K_ij K_ij     d_out[8 b + 4] = R_L  = sum_i l_i
+ *   d_out[8 b + 2] = S_LL = sum over i < j of L_ij L_ij     d_out[8 b + 5] = R_KL = sum_i k_i l_i
+ *   d_out[8 b + 6] = R_KK = sum_i k_i k_i                   d_out[8 b + 7] = R_LL = sum_i l_i l_i
+ * If d_rows is not NULL, d_rows[2 i] = k_i and d_rows[2 i + 1] = l_i for every absolute row i
+ * inside a block; rows outside every block are not written.  The statistic is the caller's (n the
+ * block's rows): U(S, Ra, Rb, Rab) = (2 S + Ra Rb / ((n - 1)(n - 2)) - 2 Rab / (n - 2)) /
+ * (n (n - 3)); HSIC_u or dCov^2_u = U(S_KL, R_K, R_L, R_KL), and the correlation divides by
+ * sqrt(U(S_KK, R_K, R_K, R_KK) U(S_LL, R_L, R_L, R_LL)).
+ *
+ * Each unordered pair is evaluated once.  A workgroup owns a super-tile of group x group tiles
+ * (tw_hsic_tile() rows per tile edge) of the triangle of super-tiles and leaves one row-sum
+ * partial per row and super-tile column in d_work; `group` in [1, 8] is that launch-plan knob
+ * (it changes which partials exist, so the last bits, never the contract), group = 0 chooses: the
+ * largest group that leaves 1024 workgroups (1 if none does), raised while d_work would pass
+ * 1 GiB.  tw_hsic_work_bytes is the size of d_work for the same arguments, 0 for shapes
+ * tw_hsic_sums refuses (n_blocks < 1, max_n < 4, group outside [0, 8], d_work past 1 GiB, a grid
+ * past 2^31 workgroups).
+ *
+ * tw_hsic_idx32 evaluates given 4-tuples: for p in [d_quad_off[s], d_quad_off[s + 1]), rows
+ * i = d_i[p], j = d_j[p], q = d_q[p], r = d_r[p] (absolute, int32), three doubles per shard:
+ *   d_out[3 s + 0] = A = sum K_ij L_ij   d_out[3 s + 1] = B = sum K_ij L_qr
+ *   d_out[3 s + 2] = C = sum K_ij L_iq
+ * (the mean of f = K_ij (L_ij + L_qr - 2 L_iq) is (A + B - 2 C) / count); an empty shard gives
+ * zeros.  tw_hsic_idx_work_bytes is 0 for sizes tw_hsic_idx32 refuses.
+ *
+ * No bit contract on the sums (floats added in the kernel's order), but: no atomics, nothing to
+ * zero, run-to-run deterministic, and a block's eight doubles and row sums (a shard's three) are
+ * the same bits alone in a launch, beside others and wherever the partition starts.  Masked pairs
+ * are selected away, so a NaN of another block never enters; a NaN coordinate of x makes the
+ * K-derived outputs of its block NaN and leaves S_LL, R_L, R_LL and every l_i as they were.
+ *
+ * TW_ERR_ARG before any device work: a null pointer (d_rows may be NULL), dx or dy outside
+ * [1, 64], a negative size, an unknown kernel id, a non-finite or positive c_x or c_y for the
+ * Gaussian kernel, max_n < 4 (a block of fewer than 4 rows has no 4-tuple), group outside [0, 8],
+ * d_work past its budget, a grid past 2^31 workgroups. */
+#define TW_HSIC_GAUSSIAN 0
+#define TW_HSIC_DISTANCE 1
+int32_t tw_hsic_tile(void);
+int64_t tw_hsic_work_bytes(int32_t n_blocks, int64_t max_n, int32_t group);
+int64_t tw_hsic_idx_work_bytes(int32_t n_shards, int64_t max_quads);
+int tw_hsic_sums(const double* d_x, int32_t dx, const double* d_y, int32_t dy,
+                 const int64_t* d_blk_off, int32_t n_blocks, int64_t max_n, int32_t kern,
+                 double c_x, double c_y, int32_t group, void* d_work, double* d_rows,
+                 double* d_out, void* stream);
+int tw_hsic_idx32(const double* d_x, int32_t dx, const double* d_y, int32_t dy,
+                  const int32_t* d_i, const int32_t* d_j, const int32_t* d_q, const int32_t* d_r,
+                  const int64_t* d_quad_off, int32_t n_shards, int64_t max_quads, int32_t kern,
+                  double c_x, double c_y, void* d_work, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ TW_KERN_PROD, TW_KERN_GINI, TW_KERN_HINGE, TW_KERN_LOGISTIC = 0, 1, 2, 3
 TW_LOSS_HINGE, TW_LOSS_LOGISTIC = 0, 1
 TW_SELF_GINI, TW_SELF_VAR, TW_SELF_KENDALL = 0, 1, 2
 TW_MMD_GAUSSIAN, TW_MMD_ENERGY = 0, 1
+TW_HSIC_GAUSSIAN, TW_HSIC_DISTANCE = 0, 1
 
 _vp, _i64, _i32, _u64, _f64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                ctypes.c_uint64, ctypes.c_double)
@@ -276,6 +277,13 @@ _SIGNATURES = {
     "tw_mmd_perm_cols": [],
     "tw_mmd_perm_work_bytes": [_i64, _i32],
     "tw_mmd_perm_sums": [_vp, _i64, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _vp],
+    "tw_hsic_tile": [],
+    "tw_hsic_work_bytes": [_i32, _i64, _i32],
+    "tw_hsic_idx_work_bytes": [_i32, _i64],
+    "tw_hsic_sums": [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _f64, _f64, _i32, _vp, _vp, _vp,
+                     _vp],
+    "tw_hsic_idx32": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f64, _f64,
+                      _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -303,6 +311,8 @@ _RESTYPES = {
     "tw_mmd_work_bytes": ctypes.c_int64,
     "tw_mmd_idx_work_bytes": ctypes.c_int64,
     "tw_mmd_perm_work_bytes": ctypes.c_int64,
+    "tw_hsic_work_bytes": ctypes.c_int64,
+    "tw_hsic_idx_work_bytes": ctypes.c_int64,
 }
 
 _lib = None

@@ -1,5 +1,5 @@
-// mmdtile.h — the tile constants, the pair function and the row loads that mmd.hip and
-// mmd_perm.hip share, so that a g has the same bits in both.
+// mmdtile.h — the tile constants, the pair function and the row loads that mmd.hip, mmd_perm.hip
+// and hsic.hip share, so that a g has the same bits in all of them.
 #pragma once
 #include "tw_common.h"
 #include "tripdist.h"

@@ -17,13 +17,14 @@ constexpr int kTripDC = 8;                    // coordinates of a lane's points 
 
 // One chunk of coordinates [c0, c0 + kTripDC) of this lane's points against every anchor of the
 // tile: the anchor's coordinate is one wave-uniform LDS read (a broadcast), used for kTripR
-// points.  TAIL: the chunk runs past d (block-uniform tests, no lane diverges).
-template <bool TAIL>
+// points.  TAIL: the chunk runs past d (block-uniform tests, no lane diverges).  TA: the anchors
+// of the micro-tile (kTripTA everywhere but hsic.hip, which holds two sides' accumulators).
+template <bool TAIL, int TA = kTripTA>
 __device__ __forceinline__ void trip_chunk(const double* __restrict__ sa, int c0, int d,
                                            const double (&pc)[kTripR][kTripDC],
-                                           double (&acc)[kTripTA][kTripR]) {
+                                           double (&acc)[TA][kTripR]) {
 #pragma unroll
-  for (int a = 0; a < kTripTA; ++a) {
+  for (int a = 0; a < TA; ++a) {
 #pragma unroll
     for (int c = 0; c < kTripDC; ++c) {
       if (!TAIL || c0 + c < d) {
