@@ -33,7 +33,11 @@ relabels the pooled sample: every permutation's three sums come from ONE launch 
 each g(w_i, w_j) once per pass of tw_mmd_perm_cols() permutations and multiplies it by the 0 / 1
 labels on the float64 matrix unit.  A column's sums depend only on the rows and on that column's
 labels, bit for bit, so a permutation that reproduces the observed split compares equal to the
-observed value.  A NaN coordinate anywhere makes every column NaN.
+observed value.  A NaN or, under the energy kernel, an overflowing distance (D = +inf, g = +inf)
+anywhere in the pooled sample makes all three sums of every column NaN (0 * inf in the label
+products, inf - inf in the identities): permutation_test then returns a NaN statistic, an all-NaN
+null and pvalue = 1 / (n_perm + 1).  Under the Gaussian kernel a pair with D = +inf is a term of
+exactly 0 and every column is finite.
 """
 from __future__ import annotations
 
