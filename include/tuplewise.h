@@ -1444,6 +1444,49 @@ int tw_hsic_idx32(const double* d_x, int32_t dx, const double* d_y, int32_t dy,
                   const int64_t* d_quad_off, int32_t n_shards, int64_t max_quads, int32_t kern,
                   double c_x, double c_y, void* d_work, double* d_out, void* stream);
 
+/* ---- The permutation test of the independence statistics above (csrc/hsic_perm.hip;
+ * tuplewise.hsic_perm permutation_sums / permutation_test; an extension): the
+ * two of tw_hsic_sums' eight sums that a permutation of the pairing moves, for EVERY permutation
+ * in one launch.  One side is held and one is moved: d_held is (n, d_h) and d_moved (n, d_m) float64
+ * row-major, H_ij = g(D(held_i, held_j); c_held) and M_ab = g(D(moved_a, moved_b); c_moved) with
+ * D, g and kern (TW_HSIC_GAUSSIAN / TW_HSIC_DISTANCE) as above, so an H_ij has the bits
+ * tw_hsic_sums gives it.  d_idx is (n_cols, n) int32 row-major: under column p item i pairs
+ * held_i with moved_{idx[p][i]}.  d_rows_held and d_rows_moved are the n row sums of H and of M
+ * on the unpermuted sample (tw_hsic_sums' d_rows, one side each).  For every column p
+ *   d_out[2 p + 0] = S_p   = sum over i < j of H_ij M_{idx[p][i], idx[p][j]}
+ *   d_out[2 p + 1] = Rab_p = sum over i of rows_held[i] rows_moved[idx[p][i]]
+ * and HSIC_u (dCov^2_u) of the permuted pairing is U(S_p, R_held, R_moved, Rab_p) with the two R
+ * of the unpermuted sample.  The entry does not know which side is X: to move X pass the inverse
+ * permutation, Y as the held side and the row sums swapped (the same two mathematical sums).
+ *
+ * The held side is evaluated once per tw_hsic_perm_cols() columns (a chunk), the moved side per
+ * column on gathered rows.  A workgroup owns a chunk and a run of consecutive tile pairs of the
+ * triangle of tw_hsic_tile()-row tiles and leaves one double per column in d_work
+ * (tw_hsic_perm_work_bytes bytes, nothing to zero); `wgs` > 0 bounds the workgroups per chunk
+ * (ceil(pairs / ceil(pairs / wgs)) are used), wgs = 0 chooses (at most 512).  No atomics: a
+ * column's partials and its Rab are added in a fixed order.  Results are run-to-run
+ * deterministic, and a column's two doubles depend only on the data, on that column's index row
+ * and on wgs — not on its position p, on n_cols or on the other columns.
+ *
+ * Every gathered index is clamped into [0, n) (as unsigned) before it addresses a row, so the
+ * device reads inside the arrays whatever d_idx holds; the sums are unspecified for rows of d_idx
+ * that are not permutations of 0 .. n - 1.  Masked pairs are selected to 0.0.  A NaN coordinate
+ * on either side makes S_p NaN in every column (every permutation meets every row).  Under the
+ * Gaussian kernel D = +inf gives g = exp(-inf) = 0 exactly (c < 0).  Under the distance kernel an
+ * overflowing D = +inf gives g = sqrt(+inf) = +inf: the term H M is +inf, or NaN where the other
+ * side's value is exactly 0 (equal rows), and S_p is +inf or NaN accordingly.
+ *
+ * TW_ERR_ARG before any device work: a null pointer, d_h or d_m outside [1, 64], n < 4 or
+ * >= 2^31, n_cols < 1, an unknown kernel id, a non-finite or positive c_held or c_moved for the
+ * Gaussian kernel, wgs < 0, a grid past 2^31 workgroups.  tw_hsic_perm_work_bytes is 0 for the
+ * sizes tw_hsic_perm_sums refuses. */
+int32_t tw_hsic_perm_cols(void);
+int64_t tw_hsic_perm_work_bytes(int64_t n, int32_t n_cols, int32_t wgs);
+int tw_hsic_perm_sums(const double* d_held, int32_t d_h, const double* d_moved, int32_t d_m,
+                      int64_t n, const int32_t* d_idx, int32_t n_cols, const double* d_rows_held,
+                      const double* d_rows_moved, int32_t kern, double c_held, double c_moved,
+                      int32_t wgs, void* d_work, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

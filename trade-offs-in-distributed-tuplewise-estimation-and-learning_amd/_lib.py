@@ -284,6 +284,10 @@ _SIGNATURES = {
                      _vp],
     "tw_hsic_idx32": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f64, _f64,
                       _vp, _vp, _vp],
+    "tw_hsic_perm_cols": [],
+    "tw_hsic_perm_work_bytes": [_i64, _i32, _i32],
+    "tw_hsic_perm_sums": [_vp, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _f64, _f64, _i32,
+                          _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -313,6 +317,7 @@ _RESTYPES = {
     "tw_mmd_perm_work_bytes": ctypes.c_int64,
     "tw_hsic_work_bytes": ctypes.c_int64,
     "tw_hsic_idx_work_bytes": ctypes.c_int64,
+    "tw_hsic_perm_work_bytes": ctypes.c_int64,
 }
 
 _lib = None

@@ -30,6 +30,7 @@
 #include "selfreduce.h"
 #include "tripdist.h"
 #include "mmdtile.h"  // kMmdT, kMmdSA, mmd_g, mmd_load (shared with mmd.hip, mmd_perm.hip)
+#include "hsictile.h"  // kHsicTA, kHsicSA, hsic_stage, hsic_side, hsic_ok (shared with hsic_perm.hip)
 #include <algorithm>
 #include <cmath>
 
@@ -40,10 +41,6 @@ constexpr int kHsicRowsPerWg = kWave;                   // rows per workgroup of
 constexpr int kHsicQPT = 4;                             // 4-tuples per lane (tw_hsic_idx32)
 constexpr int64_t kHsicWorkBudget = 1ll << 30;          // bytes of d_work a launch may ask for
 constexpr int64_t kHsicMinWgs = 2 * 2 * 256;            // two rounds on 256 CUs x 2 workgroups
-constexpr int kHsicTA = 8;                              // anchors per wave and step: two sides'
-                                                        // accumulators beside each other in VGPRs
-constexpr int kHsicSA = (kBlock / kWave) * kHsicTA;     // anchors staged per step, both sides
-static_assert(kMmdT % kHsicSA == 0, "a tile is a whole number of anchor steps");
 static_assert(kHsicTA == 8 && kTripR == 2 && kWave == 64, "hsic_anchor_sums' butterfly");
 static_assert(kBlock / kWave * kMmdT * 2 <= kHsicSA * kTripMaxD, "the point scratch aliases sax");
 static_assert(2 * kMmdT == kBlock, "one thread per point and side in the point-side combine");
@@ -136,49 +133,8 @@ __device__ __forceinline__ int hsic_anchor_of(int lane) {
 }
 __device__ __forceinline__ bool hsic_anchor_lane(int lane) { return (lane & ~0xB) == 0; }
 
-// The step's anchors: up to kHsicSA rows of d doubles from `src`, row stride kTripMaxD in LDS,
-// zeros past the tile's end (`left` anchors remain).
-__device__ __forceinline__ void hsic_stage(double* __restrict__ sa, const double* __restrict__ src,
-                                           int d, int left) {
-  for (int q = threadIdx.x; q < kHsicSA * d; q += kBlock) {
-    const int a = q / d, cc = q - a * d;
-    sa[a * kTripMaxD + cc] = a < left ? src[q] : 0.0;
-  }
-}
-
-// acc += the squared distances of this lane's points (coordinates [0, 8) already in pc) to the
-// wave's anchors: k_mmd_sums' chunk loop, the next chunk's loads issued before this chunk's
-// arithmetic.
-__device__ __forceinline__ void hsic_side(const double* __restrict__ const (&row)[kTripR], int d,
-                                          const double* __restrict__ swave,
-                                          double (&pc)[kTripR][kTripDC],
-                                          double (&acc)[kHsicTA][kTripR]) {
-  const int n_full = d / kTripDC;
-  const bool tail = n_full * kTripDC < d;
-  for (int ch = 0; ch < n_full; ++ch) {
-    double pn[kTripR][kTripDC];
-    const int c1 = (ch + 1) * kTripDC;
-    if (ch + 1 < n_full) mmd_load<false>(row, c1, d, pn);
-    else if (tail) mmd_load<true>(row, c1, d, pn);
-    trip_chunk<false, kHsicTA>(swave, ch * kTripDC, d, pc, acc);
-#pragma unroll
-    for (int r = 0; r < kTripR; ++r)
-#pragma unroll
-      for (int cc = 0; cc < kTripDC; ++cc) pc[r][cc] = pn[r][cc];
-  }
-  if (tail) trip_chunk<true, kHsicTA>(swave, n_full * kTripDC, d, pc, acc);
-}
-
-// The fold, one side at a time so that only one side's distances are live beside the other's g
-// values.  MASK: anchors past the tile's end, points past the end and, on a diagonal tile,
-// anchor <= point add nothing anywhere (selects, so a NaN of a masked pair does not enter).
-// diag_shift: 0 on a diagonal tile (anchor index above the point's), else past every point.
-template <bool MASK>
-__device__ __forceinline__ bool hsic_ok(int a, int r, int a_first, int na, int diag_shift, int lane,
-                                        const bool (&valid)[kTripR]) {
-  return !MASK || (valid[r] && a_first + a < na && a_first + a + diag_shift > r * kWave + lane);
-}
-
+// (hsic_stage, hsic_side and hsic_ok are hsictile.h's.)  The fold runs one side at a time so that
+// only one side's distances are live beside the other's g values.
 // The X side: ak becomes K (masked), S_KK, the lane's points' k terms, the anchors' terms vk.
 template <int K, bool MASK>
 __device__ __forceinline__ void hsic_fold_k(double (&ak)[kHsicTA][kTripR], double cx, int a_first,

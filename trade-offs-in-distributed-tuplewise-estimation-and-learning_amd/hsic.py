@@ -34,6 +34,8 @@ The sums are floats added in the kernel's order: no bit contract, but run-to-run
 and a block's sums are the same bits alone or beside other blocks.  The estimators mirror
 tuplewise.mmd for the proportional partition without replacement: the host owns the shuffle and
 the draws (NumPy's global legacy RNG, in NumPy's order), the device the arithmetic.
+
+The permutation test that judges Un is its own module, tuplewise.hsic_perm.
 """
 from __future__ import annotations
 
