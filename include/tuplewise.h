@@ -274,6 +274,20 @@ int32_t tw_count_chain_class_digits(int32_t w);
  * 4 where it runs the wide digits, 3 anywhere else (where the launch runs no digit loop — see
  * tw_count_chain_class_form — the setting has no effect). */
 int32_t tw_count_chain_class_digits_of(int32_t nb, int32_t k);
+/* A/B control of how the class-run form's pre-passes are launched.  0 (automatic)
+ * and 2: one launch (k_chain_prepass) builds the planes, sorts every bag's z images into class
+ * runs — in registers, one pass over global memory, for bags of up to 16384 z images — and
+ * zeroes the counts; 1: the separate launches (the zeroing, k_chain_planes, k_chain_zclasses);
+ * -1 only reports.  Returns the setting in force before the call; any other value changes
+ * nothing and returns TW_ERR_ARG.  Process-global; same counts, same workspace regions: every
+ * launch rewrites its regions before its count, so the forms may alternate on one workspace. */
+int32_t tw_count_chain_prepass(int32_t mode);
+/* The form a strict tw_count_pairs_chain_planes launch with these arguments runs under the
+ * current settings: 0 no pre-pass (the packed kernel), 1 separate launches (also every launch
+ * without class bits), 2 fused with every bag sorted in registers, 3 fused with the two-pass
+ * streaming loop for the bags of more than 16384 z images. */
+int32_t tw_count_chain_prepass_of(int32_t n_shards, int32_t steps, int64_t max_nx,
+                                  int64_t max_nz, int64_t image_bound);
 /* The same counts as tw_count_pairs_chain in O(n + m) per bag (algo="sorted", SURVEY row f4;
  * estimation-experiment/main.py:29-31's integer): each bag's z images (integers in
  * [0, z_total], z_total = the Z count the images were ranked against) counting-sorted into

@@ -19,4 +19,6 @@ python3 tools/pmc_summary.py $O/chain_emit_pmc.json k_chain_emit $O/p1 $O/p2 $O/
 # the count's pre-passes (the planes; with class bits the class-ordered z and the run tables)
 python3 tools/pmc_summary.py $O/chain_planes_pmc.json k_chain_planes $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null
 python3 tools/pmc_summary.py $O/chain_zclasses_pmc.json k_chain_zclasses $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null 2>&1 || true  # (none without class bits)
+# (the fused form of the two, DESIGN §4.1l: none under tw_count_chain_prepass 1)
+python3 tools/pmc_summary.py $O/chain_prepass_pmc.json k_chain_prepass $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null 2>&1 || true
 echo done

@@ -20,7 +20,8 @@ path, K, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
 # (the strict count: the packed k_count_chain<R, false>, the plane-reading
 # k_count_chain_planes<NB>, whose launch's time includes its pre-pass k_chain_planes<NB>, the
 # launch just before it on the stream, or its class-run form k_count_chain_classes<NB, K>, whose
-# time includes both pre-passes: k_chain_planes<NB> and k_chain_zclasses)
+# time includes both pre-passes: k_chain_planes<NB> and k_chain_zclasses, or the one launch
+# that runs both, k_chain_prepass<NB>)
 every = list(csv.DictReader(open(path)))
 rows = [r for r in every
         if ("k_count_chain<" in r["Kernel_Name"] and ", false>" in r["Kernel_Name"])
@@ -30,19 +31,30 @@ pre = sorted((r for r in every if "k_chain_planes<" in r["Kernel_Name"]),
              key=lambda r: int(r["Start_Timestamp"]))
 pre2 = sorted((r for r in every if "k_chain_zclasses" in r["Kernel_Name"]),
               key=lambda r: int(r["Start_Timestamp"]))
+fused = sorted((r for r in every if "k_chain_prepass<" in r["Kernel_Name"]),
+               key=lambda r: int(r["Start_Timestamp"]))
 grid = lambda r: int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)
 dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
 g = max(grid(r) for r in rows)
 big = sorted((r for r in rows if grid(r) == g), key=lambda r: int(r["Start_Timestamp"]))
 
 
-def last_before(qs, r):
+def last_row_before(qs, r):
     before = [q for q in qs if int(q["Start_Timestamp"]) < int(r["Start_Timestamp"])]
-    return dur(before[-1]) if before else 0.0
+    return before[-1] if before else None
+
+
+def last_before(qs, r):
+    q = last_row_before(qs, r)
+    return dur(q) if q is not None else 0.0
 
 
 def prepass_ms(r):
     if "k_count_chain_classes<" in r["Kernel_Name"]:
+        f, z = last_row_before(fused, r), last_row_before(pre2, r)
+        # (the form of THIS launch: whichever pre-pass ran last before it)
+        if f is not None and (z is None or int(f["Start_Timestamp"]) > int(z["Start_Timestamp"])):
+            return dur(f)
         return last_before(pre, r) + last_before(pre2, r)
     if "k_count_chain_planes<" not in r["Kernel_Name"]:
         return 0.0

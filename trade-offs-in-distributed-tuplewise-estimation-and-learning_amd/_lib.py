@@ -257,6 +257,8 @@ _SIGNATURES = {
     "tw_count_chain_class_span": [_i32],
     "tw_count_chain_class_digits": [_i32],
     "tw_count_chain_class_digits_of": [_i32, _i32],
+    "tw_count_chain_prepass": [_i32],
+    "tw_count_chain_prepass_of": [_i32, _i32, _i64, _i64, _i64],
     "tw_triplet_rows_tile": [],
     "tw_triplet_rows": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp,
                         _vp, _vp, _vp],

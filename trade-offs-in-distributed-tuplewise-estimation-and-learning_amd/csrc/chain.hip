@@ -633,19 +633,17 @@ __global__ __launch_bounds__(kBlock) void k_count_chain(
 // Only the groups the bag's items read are written: its full x groups (and a padded last one
 // where the remainder is not swapped), its z groups where it is.
 template <int NB>
-__global__ __launch_bounds__(kBlock) void k_chain_planes(
-    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
-    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
-    int n_shards, int n_bags, int gx, int gz, int swap, uint32_t* __restrict__ work) {
+__device__ __forceinline__ void chain_planes_wave(
+    int64_t block, const float* __restrict__ xb, const int64_t* __restrict__ x_off,
+    int64_t x_stride, const float* __restrict__ zb, const int64_t* __restrict__ z_off,
+    int64_t z_stride, int n_shards, int n_bags, int gx, int gz, int swap,
+    uint32_t* __restrict__ work) {
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int lane = threadIdx.x & (kWave - 1);
-  int64_t w = (int64_t)blockIdx.x * (kBlock / kWave) + wid;
-  const int64_t x_waves = (int64_t)n_bags * gx;
-  const bool zside = w >= x_waves;
-  const int G = zside ? gz : gx;
-  if (zside) w -= x_waves;
-  if (G == 0 || w >= (int64_t)n_bags * G) return;
-  const int v = (int)(w / G), g = (int)(w - (int64_t)v * G);
+  const PlanesWave pw = planes_wave(block * (kBlock / kWave) + wid, n_bags, gx, gz);
+  if (!pw.active) return;
+  const bool zside = pw.zside;
+  const int v = pw.bag, g = pw.g;
   const int c = v / n_shards, s = v - c * n_shards;
   const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
   const PlanesBag bag = planes_bag(nx, nz, swap != 0);
@@ -666,10 +664,18 @@ __global__ __launch_bounds__(kBlock) void k_chain_planes(
     a[k] = k * 64 + lane < cnt ? img : (zside ? kBitsZNever : 0u);
   }
   bits_transpose32(a);
-  uint32_t* __restrict__ dst =
-      work + bits_uniform(planes_word(NB, (zside ? x_waves : 0) + w, 0, 0));
+  uint32_t* __restrict__ dst = work + bits_uniform(planes_word(NB, pw.group, 0, 0));
 #pragma unroll
   for (int b = 0; b < NB; ++b) dst[b * 64 + lane] = a[b];
+}
+
+template <int NB>
+__global__ __launch_bounds__(kBlock) void k_chain_planes(
+    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int gx, int gz, int swap, uint32_t* __restrict__ work) {
+  chain_planes_wave<NB>(blockIdx.x, xb, x_off, x_stride, zb, z_off, z_stride, n_shards, n_bags,
+                        gx, gz, swap, work);
 }
 
 // The count on those planes: work items of chainplan.h (a plane item: up to p.R x groups
@@ -742,16 +748,70 @@ __device__ __forceinline__ uint32_t class_block_scan(uint32_t v, uint32_t* wsum,
   return v + add;  // inclusive
 }
 
-__global__ __launch_bounds__(kBlock) void k_chain_zclasses(
-    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
-    int n_shards, int n_bags, int nb, ClassPlan cp, uint32_t* __restrict__ work) {
-  static_assert(kBlock == 1 << kClassMaxBits, "one thread per class");
-  __shared__ uint32_t hist[kBlock], wsum[kBlock / kWave];
+// the word pre-pass 2 stores for a complemented z image under the launch's loop
+__device__ __forceinline__ uint32_t class_store_word(uint32_t zc, const ClassPlan& cp) {
+  return cp.digits <= 0                 ? zc
+         : cp.dbits == kClassWideBits ? class_wide_encode(zc)
+                                      : class_digit_encode(zc, cp.digits);
+}
+
+// The same word from the launch's form spelled out once per block: digit j is sh[j], mk[j]
+struct ClassStoreForm {
+  bool plain;  // the complemented image itself
+  int sh[kClassDigits];
+  uint32_t mk[kClassDigits];
+};
+__device__ __forceinline__ ClassStoreForm class_store_form(const ClassPlan& cp) {
+  ClassStoreForm e{};
+  e.plain = cp.digits <= 0;
+  const bool wide = cp.dbits == kClassWideBits;
+  const int nl = e.plain ? kClassDigitMaxNL : cp.digits;
+#pragma unroll
+  for (int j = 0; j < kClassDigits; ++j) {
+    e.sh[j] = wide ? kClassWideBits * j : class_digit_shift(nl, j);
+    e.mk[j] = wide ? (j < kClassWideDigits ? (1u << kClassWideBits) - 1u : 0u)
+                   : (1u << class_digit_width(nl, j)) - 1u;
+  }
+  return e;
+}
+__device__ __forceinline__ uint32_t class_store_word(uint32_t zc, const ClassStoreForm& e) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int j = 0; j < kClassDigits; ++j) w |= ((zc >> e.sh[j]) & e.mk[j]) << (8 * j);
+  return e.plain ? zc : w;
+}
+
+// From the bag's class histogram in hist (one thread per class, all of it written): the bag's
+// entry count and run table go to the workspace and hist becomes the classes' first positions
+// c0 in the class-ordered region.  Ends behind a barrier.  SMALL: a bag of at most kPrepassCap
+// images, whose runs are cut in 32-bit arithmetic (class_run32: the same runs).
+template <bool SMALL = false>
+__device__ __forceinline__ void class_block_tables(uint32_t* hist, uint32_t* wsum, int v,
+                                                   const ClassPlan& cp,
+                                                   uint32_t* __restrict__ work) {
   const int t = threadIdx.x, lane = t & (kWave - 1), wid = t / kWave;
-  const int v = blockIdx.x;  // < n_bags
-  const int c = v / n_shards, s = v - c * n_shards;
-  const int64_t nz = z_off[s + 1] - z_off[s];
-  const float* __restrict__ src = zb + ((int64_t)c * z_stride + z_off[s]);
+  const uint32_t n = hist[t];  // (classes >= 2^k: 0)
+  const uint32_t nr = (uint32_t)class_runs(n, cp.chunk);
+  const uint32_t c0 = class_block_scan(n, wsum, lane, wid) - n;
+  const uint32_t e1 = class_block_scan(nr, wsum, lane, wid), e0 = e1 - nr;
+  hist[t] = c0;  // (every thread read its own count above)
+  if (t == kBlock - 1) work[cp.off_cnt + v] = e1;  // <= cp.cap (class_capacity)
+  uint32_t* __restrict__ tab = work + (cp.off_tab + (int64_t)v * 2 * cp.cap);
+  for (uint32_t j = 0; j < nr; ++j) {
+    const ClassRun r =
+        SMALL ? class_run32(c0, n, nr, j, (uint32_t)t) : class_run(c0, n, nr, j, (uint32_t)t);
+    tab[2 * (e0 + j)] = class_entry_lo(r);
+    tab[2 * (e0 + j) + 1] = class_entry_hi(r);
+  }
+  __syncthreads();
+}
+
+// A bag of any size: two passes over its images in global memory
+__device__ __forceinline__ void chain_zclasses_stream(const float* __restrict__ src, int64_t nz,
+                                                      int v, int nb, const ClassPlan& cp,
+                                                      uint32_t* hist, uint32_t* wsum,
+                                                      uint32_t* __restrict__ work) {
+  const int t = threadIdx.x;
   hist[t] = 0;
   __syncthreads();
   constexpr int U = 8;  // loads in flight per thread: a block walks its whole bag
@@ -764,19 +824,7 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
       if (i0 + u * kBlock < nz) atomicAdd(&hist[class_of(bits_z_image(f[u]), nb, cp.k)], 1u);
   }
   __syncthreads();
-  const uint32_t n = hist[t];  // (classes >= 2^k: 0)
-  const uint32_t nr = (uint32_t)class_runs(n, cp.chunk);
-  const uint32_t c0 = class_block_scan(n, wsum, lane, wid) - n;
-  const uint32_t e1 = class_block_scan(nr, wsum, lane, wid), e0 = e1 - nr;
-  hist[t] = c0;  // now the class's cursor (every thread read its own count above)
-  if (t == kBlock - 1) work[cp.off_cnt + v] = e1;  // <= cp.cap (class_capacity)
-  uint32_t* __restrict__ tab = work + (cp.off_tab + (int64_t)v * 2 * cp.cap);
-  for (uint32_t j = 0; j < nr; ++j) {
-    const ClassRun r = class_run(c0, n, nr, j, (uint32_t)t);
-    tab[2 * (e0 + j)] = class_entry_lo(r);
-    tab[2 * (e0 + j) + 1] = class_entry_hi(r);
-  }
-  __syncthreads();
+  class_block_tables(hist, wsum, v, cp, work);  // hist: now the classes' cursors
   uint32_t* __restrict__ zs = work + (cp.off_zs + (int64_t)v * cp.zs_stride);
   for (int64_t i0 = t; i0 < nz; i0 += kBlock * U) {
     float f[U];
@@ -787,11 +835,113 @@ __global__ __launch_bounds__(kBlock) void k_chain_zclasses(
       const uint32_t zc = bits_z_image(f[u]);
       if (i0 + u * kBlock < nz)
         zs[atomicAdd(&hist[class_of(zc, nb, cp.k)], 1u)] =  // < c0 + n <= nz
-            cp.digits <= 0                 ? zc
-            : cp.dbits == kClassWideBits ? class_wide_encode(zc)
-                                         : class_digit_encode(zc, cp.digits);
+            class_store_word(zc, cp);
     }
   }
+}
+
+__global__ __launch_bounds__(kBlock) void k_chain_zclasses(
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int nb, ClassPlan cp, uint32_t* __restrict__ work) {
+  static_assert(kBlock == 1 << kClassMaxBits, "one thread per class");
+  __shared__ uint32_t hist[kBlock], wsum[kBlock / kWave];
+  const int v = blockIdx.x;  // < n_bags
+  const int c = v / n_shards, s = v - c * n_shards;
+  const int64_t nz = z_off[s + 1] - z_off[s];
+  const float* __restrict__ src = zb + ((int64_t)c * z_stride + z_off[s]);
+  chain_zclasses_stream(src, nz, v, nb, cp, hist, wsum, work);
+}
+
+// The same sort with the bag in registers: 1 <= nz <= kBlock * PER images, PER
+// per thread, every load issued before the first use and every image read from global memory
+// once.  The histogram's returning atomic is already the image's index inside its class: it
+// stays beside the image (16 bits: below kPrepassCap), the classes' first positions come from
+// the same scans as above, and the image goes to c0[class] + index.  hist: kBlock + 1 words.
+template <int PER>
+__device__ __forceinline__ void chain_zclasses_resident(const float* __restrict__ src, int nz,
+                                                        int v, int nb, const ClassPlan& cp,
+                                                        uint32_t* hist, uint32_t* wsum,
+                                                        uint32_t* __restrict__ work) {
+  static_assert(PER % 2 == 0 && (int64_t)kBlock * PER <= kPrepassCap, "chainclass.h's capacity");
+  const int t = threadIdx.x;
+  if (t == 0) hist[kBlock] = 0;
+  hist[t] = 0;
+  __syncthreads();
+  float f[PER];
+  uint32_t at[PER / 2];  // the indices of images 2 j and 2 j + 1
+  // image u * kBlock + t exists: whole rows by a scalar test, one lane mask for the last row
+  const int full = nz / kBlock;
+  const bool tail = t < nz - full * kBlock;
+  auto has = [&](int u) { return u < full || (u == full && tail); };
+#pragma unroll
+  for (int u = 0; u < PER; ++u)  // (u32 offsets from the uniform base: one register each)
+    f[u] = src[min((uint32_t)(u * kBlock + t), (uint32_t)(nz - 1))];
+  // (batches of kB images behind scheduling barriers: left to itself the compiler keeps every
+  // image's class, index and address live at once, 242 VGPRs)
+  constexpr int kB = 8;
+  static_assert(PER % kB == 0 && kB % 2 == 0, "whole batches, whole index pairs");
+#pragma unroll
+  for (int u0 = 0; u0 < PER; u0 += kB) {
+#pragma unroll
+    for (int u = u0; u < u0 + kB; ++u) {
+      // (no branch: a slot past the bag's end counts into the spare word behind the classes)
+      const uint32_t cls = class_of(bits_z_image(f[u]), nb, cp.k);  // (f[u]: a clamped load)
+      const uint32_t idx = atomicAdd(&hist[has(u) ? cls : kBlock], 1u);  // < kBlock * PER
+      at[u / 2] = u % 2 ? at[u / 2] | (idx << 16) : idx;
+      // (the pair is made here, not where the scatter reads it: one register per two images)
+      if (u % 2) asm volatile("" : "+v"(at[u / 2]));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  class_block_tables<true>(hist, wsum, v, cp, work);  // hist: now c0 of every class
+  uint32_t* __restrict__ zs = work + (cp.off_zs + (int64_t)v * cp.zs_stride);
+  const ClassStoreForm enc = class_store_form(cp);
+#pragma unroll
+  for (int u0 = 0; u0 < PER; u0 += kB) {
+#pragma unroll
+    for (int u = u0; u < u0 + kB; ++u) {
+      float fu = f[u];  // (opaque: the class is computed again, not kept from the histogram)
+      asm volatile("" : "+v"(fu));
+      const uint32_t zc = bits_z_image(fu);
+      const uint32_t idx = u % 2 ? at[u / 2] >> 16 : at[u / 2] & 0xFFFFu;
+      if (has(u))
+        zs[hist[class_of(zc, nb, cp.k)] + idx] = class_store_word(zc, enc);  // < c0 + n <= nz
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// Both pre-passes of the class-run form in one launch (chainclass.h's prepass_grid; DESIGN
+// §4.1l).  Blocks [0, n_bags): the z-class role of one bag — in registers where the bag fits
+// (block-uniform), the streaming loop for any other size — and the bag's count zeroed, which
+// the count kernels behind the launch add to.  The blocks after them: k_chain_planes' waves.
+// The roles write disjoint regions and no block waits for another.
+template <int NB>
+__global__ __launch_bounds__(kBlock) void k_chain_prepass(
+    const float* __restrict__ xb, const int64_t* __restrict__ x_off, int64_t x_stride,
+    const float* __restrict__ zb, const int64_t* __restrict__ z_off, int64_t z_stride,
+    int n_shards, int n_bags, int gx, int gz, int swap, ClassPlan cp,
+    uint32_t* __restrict__ work, unsigned long long* __restrict__ out) {
+  static_assert(kBlock == kPrepassThreads && kBlock == 1 << kClassMaxBits, "chainclass.h");
+  __shared__ uint32_t hist[kBlock + 1], wsum[kBlock / kWave];
+  if (blockIdx.x >= (unsigned)n_bags) {
+    chain_planes_wave<NB>((int64_t)blockIdx.x - n_bags, xb, x_off, x_stride, zb, z_off, z_stride,
+                          n_shards, n_bags, gx, gz, swap, work);
+    return;
+  }
+  const int v = blockIdx.x;
+  const int c = v / n_shards, s = v - c * n_shards;
+  const int64_t nz = z_off[s + 1] - z_off[s];
+  const float* __restrict__ src = zb + ((int64_t)c * z_stride + z_off[s]);
+  if (threadIdx.x == 0) out[v] = 0ull;
+  const int per = prepass_per_thread(nz);
+  if (per == kPrepassPerSmall)
+    chain_zclasses_resident<kPrepassPerSmall>(src, (int)nz, v, NB, cp, hist, wsum, work);
+  else if (per == kPrepassPer)
+    chain_zclasses_resident<kPrepassPer>(src, (int)nz, v, NB, cp, hist, wsum, work);
+  else
+    chain_zclasses_stream(src, nz, v, NB, cp, hist, wsum, work);
 }
 
 // The count on class runs: per bag p.tiles_x x class_spans(cp.cap, cp.span) class items
@@ -1059,6 +1209,13 @@ static int g_planes_swap = 1;  // (tw_count_chain_set_swap: 0 never, 1 automatic
 static int g_class_bits = -1;  // (tw_count_chain_set_class_bits: -1 automatic, 0 off, 1..8)
 static int g_class_span = 0;   // (tw_count_chain_class_span: 0 automatic, >= 1 entries per item)
 static int g_class_digits = 0;  // (tw_count_chain_class_digits: 0 automatic, 3 or 4 planes)
+static int g_prepass = 0;  // (tw_count_chain_prepass: 0 automatic, 1 separate launches, 2 fused)
+// class bits of a bit-sliced launch: forced (clamped to its planes), or chainclass.h's
+// automatic rule
+static int chain_class_bits(int64_t max_nz, int64_t bags, int nb) {
+  return g_class_bits < 0 ? class_bits_auto(max_nz, bags, nb)
+                          : std::min(g_class_bits, std::min(kClassMaxBits, nb - 8));
+}
 
 // strict: R in {16, 8} x-images per lane, least padded slots (ties to 16); half: R = 8 {g, h}
 // pairs (the same 8 packed registers per lane).  z chunks: as many as give ~150 work items per
@@ -1483,7 +1640,8 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
                                    const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                                    int32_t n_shards, int32_t steps, int64_t max_nx,
                                    int64_t max_nz, int32_t half, int64_t image_bound,
-                                   uint64_t* d_out, void* d_work, hipStream_t st);
+                                   uint64_t* d_out, void* d_work, hipStream_t st,
+                                   bool zero_out);
 }  // namespace tw
 
 extern "C" int tw_count_pairs_chain(const void* d_x_bag, const int64_t* d_x_off,
@@ -1554,7 +1712,8 @@ static int chain_unpack_count_impl(const uint64_t* d_recv, int32_t world, int32_
   TW_LAUNCH_CHECK();
   if (d_work != nullptr)  // (tw_chain_unpack_count_planes; its workspace checked there)
     return count_chain_launch_work(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
-                                   max_nx, max_nz, half, image_bound, d_out, d_work, st);
+                                   max_nx, max_nz, half, image_bound, d_out, d_work, st,
+                                   /*zero_out=*/false);  // (k_zero_two above)
   return count_chain_launch(d_x_bag, d_x_off, n_x, d_z_bag, d_z_off, n_z, n_shards, steps,
                             max_nx, max_nz, half, d_out, st);
 }
@@ -1603,20 +1762,30 @@ static int count_chain_launch(const void* d_x_bag, const int64_t* d_x_off, int64
 
 // The plane pre-pass and the count on its planes, back to back on st (out already zeroed);
 // with class bits (cp.k > 0) pre-pass 2 between them, the plan's swapped items if it has any
-// and the count on class runs
+// and the count on class runs.  fused (class bits only): one launch runs both pre-passes and
+// zeroes out itself (k_chain_prepass).
 template <int NB>
-static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, const float* xb,
+static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, bool fused,
+                                      const float* xb,
                                       const int64_t* d_x_off, int64_t x_stride, const float* zb,
                                       const int64_t* d_z_off, int64_t z_stride, int n_shards,
                                       int bags, uint32_t* work, unsigned long long* o,
                                       hipStream_t st) {
-  const int64_t pre = ceil_div((int64_t)bags * (p.gx + p.gz), kBlock / kWave);
-  hipLaunchKernelGGL((k_chain_planes<NB>), dim3((unsigned)pre), dim3(kBlock), 0, st, xb, d_x_off,
-                     x_stride, zb, d_z_off, z_stride, n_shards, bags, p.gx, p.gz, p.swap,
-                     work);
+  if (fused) {  // (cp.k > 0) both pre-passes and the zeroing of o in one launch
+    hipLaunchKernelGGL((k_chain_prepass<NB>),
+                       dim3((unsigned)prepass_grid(bags, p.gx, p.gz).blocks), dim3(kBlock), 0, st,
+                       xb, d_x_off, x_stride, zb, d_z_off, z_stride, n_shards, bags, p.gx, p.gz,
+                       p.swap, cp, work, o);
+  } else {
+    const int64_t pre = ceil_div((int64_t)bags * (p.gx + p.gz), kBlock / kWave);
+    hipLaunchKernelGGL((k_chain_planes<NB>), dim3((unsigned)pre), dim3(kBlock), 0, st, xb,
+                       d_x_off, x_stride, zb, d_z_off, z_stride, n_shards, bags, p.gx, p.gz,
+                       p.swap, work);
+  }
   if (cp.k > 0) {  // the class-run form: pre-pass 2, then the count on class runs
-    hipLaunchKernelGGL(k_chain_zclasses, dim3((unsigned)bags), dim3(kBlock), 0, st, zb, d_z_off,
-                       z_stride, n_shards, bags, NB, cp, work);
+    if (!fused)
+      hipLaunchKernelGGL(k_chain_zclasses, dim3((unsigned)bags), dim3(kBlock), 0, st, zb, d_z_off,
+                         z_stride, n_shards, bags, NB, cp, work);
     const int n_swapped = p.tiles_s * p.schunks;
     if (n_swapped > 0)  // the plan's swapped items, in a launch of their own (same counts)
       hipLaunchKernelGGL((k_count_chain_swapped<NB>),
@@ -1661,7 +1830,8 @@ static int64_t chain_planes_work_bytes(int64_t bags, int64_t max_nx, int64_t max
          (int64_t)sizeof(uint32_t);
 }
 
-// The count launch of the _planes entries on an output already zeroed: where chainplan.h's
+// The count launch of the _planes entries on an output already zeroed (zero_out: zeroed here,
+// by a launch of its own or inside the fused pre-pass): where chainplan.h's
 // chain_count_sliced says so, the pre-pass and k_count_chain_planes (tuning hook: R = largest
 // groups per item) or, with class bits, its class-run form (chainclass.h); everything else
 // count_chain_launch's packed kernel.
@@ -1669,16 +1839,21 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
                                    const void* d_z_bag, const int64_t* d_z_off, int64_t z_stride,
                                    int32_t n_shards, int32_t steps, int64_t max_nx,
                                    int64_t max_nz, int32_t half, int64_t image_bound,
-                                   uint64_t* d_out, void* d_work, hipStream_t st) {
+                                   uint64_t* d_out, void* d_work, hipStream_t st,
+                                   bool zero_out) {
   const int64_t bags = (int64_t)n_shards * steps;
-  if (max_nx == 0 || max_nz == 0) return TW_OK;
   const int nb = bits_pick_nb(image_bound);
-  if (!chain_count_sliced(max_nx, g_chain_R, half != 0, nb))
+  const bool sliced =
+      max_nx != 0 && max_nz != 0 && chain_count_sliced(max_nx, g_chain_R, half != 0, nb);
+  const int k = sliced ? chain_class_bits(max_nz, bags, nb) : 0;
+  // the fused pre-pass zeroes the counts itself; every other form adds to an output zeroed here
+  const bool fused = prepass_form(g_prepass, k, max_nz) != 1;
+  if (zero_out && !fused)
+    TW_HIP_CHECK(tw_zero_async(d_out, 0, sizeof(uint64_t) * (size_t)bags, st));
+  if (max_nx == 0 || max_nz == 0) return TW_OK;
+  if (!sliced)
     return count_chain_launch(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride, n_shards,
                               steps, max_nx, max_nz, half, d_out, st);
-  // class bits: forced (clamped to this launch's planes), or chainclass.h's automatic rule
-  const int k = g_class_bits < 0 ? class_bits_auto(max_nz, bags, nb)
-                                 : std::min(g_class_bits, std::min(kClassMaxBits, nb - 8));
   // (under class runs the automatic swap also asks which remainder costs fewer instructions)
   // The digit loop's register map holds kClassDigitsMaxR groups: the plan's tiles follow
   const bool digits = k > 0 && class_loop_form(nb, k) == 3;
@@ -1704,6 +1879,7 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   cp.dbits = digits ? dbits : 0;
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
                    bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&
+                   (!fused || prepass_grid_fits(bags, p.gx, p.gz)) &&
                    bags * (int64_t)cp.per_bag < (1ll << 31),
                "tw_count_pairs_chain_planes: grid too large");
   auto* o = (unsigned long long*)d_out;
@@ -1711,19 +1887,19 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   const float* zf = (const float*)d_z_bag;
   uint32_t* w = (uint32_t*)d_work;
   if (nb == 16)
-    count_chain_launch_planes<16>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<16>(p, cp, fused, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else if (nb == 18)
-    count_chain_launch_planes<18>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<18>(p, cp, fused, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else if (nb == 20)
-    count_chain_launch_planes<20>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<20>(p, cp, fused, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else if (nb == 22)
-    count_chain_launch_planes<22>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<22>(p, cp, fused, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   else
-    count_chain_launch_planes<24>(p, cp, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
+    count_chain_launch_planes<24>(p, cp, fused, xf, d_x_off, x_stride, zf, d_z_off, z_stride, n_shards,
                                   (int)bags, w, o, st);
   TW_LAUNCH_CHECK();
   return TW_OK;
@@ -1765,6 +1941,32 @@ extern "C" int32_t tw_count_chain_class_digits_of(int32_t nb, int32_t k) {
                                               : kClassDigitBits;
 }
 
+// How the pre-passes of the class-run form are launched: 0 automatic — fused
+// wherever the class form runs —, 1 the separate launches (k_zero_fill, k_chain_planes,
+// k_chain_zclasses), 2 fused wherever the class form runs, -1 only reports.  Returns the setting
+// in force before the call; anything else changes nothing and returns TW_ERR_ARG.
+extern "C" int32_t tw_count_chain_prepass(int32_t mode) {
+  const int32_t before = g_prepass;
+  if (mode == -1) return before;
+  TW_ARG_CHECK(mode >= 0 && mode <= 2,
+               "tw_count_chain_prepass: 0 (automatic), 1 (separate), 2 (fused) or -1 (report)");
+  g_prepass = mode;
+  return before;
+}
+
+// The form a strict launch of tw_count_pairs_chain_planes with these arguments runs under the
+// current settings: 0 no pre-pass (the packed kernel), 1 separate launches, 2 the fused launch
+// with every bag sorted in registers, 3 the fused launch with the streaming loop for bags past
+// kPrepassCap images
+extern "C" int32_t tw_count_chain_prepass_of(int32_t n_shards, int32_t steps, int64_t max_nx,
+                                             int64_t max_nz, int64_t image_bound) {
+  if (n_shards <= 0 || steps <= 0 || max_nx <= 0 || max_nz <= 0) return 0;
+  const int nb = bits_pick_nb(image_bound);
+  if (!chain_count_sliced(max_nx, g_chain_R, false, nb)) return 0;
+  return prepass_form(g_prepass, chain_class_bits(max_nz, (int64_t)n_shards * steps, nb),
+                      max_nz);
+}
+
 extern "C" int64_t tw_chain_planes_work_bytes(int32_t n_shards, int32_t steps, int64_t max_nx,
                                               int64_t max_nz, int32_t half,
                                               int64_t image_bound) {
@@ -1797,11 +1999,9 @@ extern "C" int tw_count_pairs_chain_planes(const void* d_x_bag, const int64_t* d
   TW_ARG_CHECK(work_bytes >= need && (need == 0 || d_work != nullptr),
                "tw_count_pairs_chain_planes: work_bytes %lld < %lld (tw_chain_planes_work_bytes)",
                (long long)work_bytes, (long long)need);
-  hipStream_t st = (hipStream_t)stream;
-  TW_HIP_CHECK(tw_zero_async(d_out, 0, sizeof(uint64_t) * (size_t)bags, st));
   return count_chain_launch_work(d_x_bag, d_x_off, x_stride, d_z_bag, d_z_off, z_stride,
                                  n_shards, steps, max_nx, max_nz, half, image_bound, d_out,
-                                 d_work, st);
+                                 d_work, (hipStream_t)stream, /*zero_out=*/true);
 }
 
 // tw_chain_unpack_count with tw_count_pairs_chain_planes' promise and count

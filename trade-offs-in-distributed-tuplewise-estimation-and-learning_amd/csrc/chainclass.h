@@ -293,6 +293,12 @@ TW_BITS_HD ClassRun class_run(int64_t c0, int64_t n, int64_t nr, int64_t j, uint
   const int64_t a = j * n / nr, b = (j + 1) * n / nr;
   return ClassRun{c0 + a, b - a, cls};
 }
+// class_run for a class of at most 2^16 images: (j + 1) * n < 2^32 (j < nr <= n), so the same
+// quotients come from 32-bit arithmetic
+TW_BITS_HD ClassRun class_run32(uint32_t c0, uint32_t n, uint32_t nr, uint32_t j, uint32_t cls) {
+  const uint32_t a = j * n / nr, b = (j + 1) * n / nr;
+  return ClassRun{(int64_t)(c0 + a), (int64_t)(b - a), cls};
+}
 TW_BITS_HD uint32_t class_entry_lo(const ClassRun& r) { return (uint32_t)r.z0 | (r.cls << 24); }
 TW_BITS_HD uint32_t class_entry_hi(const ClassRun& r) { return (uint32_t)r.len; }
 TW_BITS_HD ClassRun class_entry(uint32_t lo, uint32_t hi) {
@@ -451,6 +457,90 @@ TW_BITS_HD int class_swap_mode(int swap, int64_t max_nx, int64_t max_nz, int nb,
   const int64_t rx = max_nx % kPlaneGroup, zg = planes_ceil_div(max_nz, kPlaneGroup);
   const int64_t slot = slot_valu > 0 ? slot_valu : nb - k + 1;
   return rx * zg * (4 * nb + 5) < max_nz * 4 * slot ? 1 : 0;
+}
+
+// ------------------------------------------------------------------- the fused pre-pass grid
+// With class bits both pre-passes run as ONE launch (chain.hip's k_chain_prepass):
+// blocks [0, n_bags) sort the z images of one bag each into class runs — first in the grid, so
+// the longest blocks start first — and the blocks after them build the planes, wave w of them
+// the wave w of k_chain_planes' own grid.  The roles write disjoint regions of the workspace and
+// never wait for one another.  Everything below is what the kernel itself evaluates
+// (tests/native/chainprepass_driver.cpp enumerates it on the host).
+constexpr int kPrepassWaves = 4;  // waves of a pre-pass block (chain.hip: kBlock / kWave)
+constexpr int kPrepassThreads = 64 * kPrepassWaves;
+
+// Wave w of the plane pre-pass: the x groups of every bag [bag][gx], then the z groups
+// [bag][gz]; `group` is the wave's group of the workspace (planes_word's)
+struct PlanesWave {
+  bool active, zside;
+  int bag, g;
+  int64_t group;
+};
+TW_BITS_HD PlanesWave planes_wave(int64_t w, int64_t n_bags, int gx, int gz) {
+  PlanesWave r{};
+  const int64_t x_waves = n_bags * gx;
+  r.zside = w >= x_waves;
+  const int G = r.zside ? gz : gx;
+  const int64_t ws = r.zside ? w - x_waves : w;
+  if (w < 0 || G == 0 || ws >= n_bags * G) return r;
+  r.active = true;
+  r.bag = (int)(ws / G);
+  r.g = (int)(ws - (int64_t)r.bag * G);
+  r.group = w;  // (x side: w; z side: x_waves + ws, the same number)
+  return r;
+}
+
+struct PrepassGrid {
+  int64_t zblocks;  // the z-class blocks, one per bag: block indices [0, zblocks)
+  int64_t pblocks;  // the plane blocks after them, kPrepassWaves waves each
+  int64_t blocks;
+};
+TW_BITS_HD PrepassGrid prepass_grid(int64_t n_bags, int gx, int gz) {
+  PrepassGrid g{};
+  g.zblocks = n_bags;
+  g.pblocks = planes_ceil_div(n_bags * ((int64_t)gx + gz), kPrepassWaves);
+  g.blocks = g.zblocks + g.pblocks;
+  return g;
+}
+// a grid the launch takes: its block count and the plane waves stay below 2^31
+TW_BITS_HD bool prepass_grid_fits(int64_t n_bags, int gx, int gz) {
+  return prepass_grid(n_bags, gx, gz).blocks < ((int64_t)1 << 31) &&
+         n_bags * ((int64_t)gx + gz) < ((int64_t)1 << 31);
+}
+
+enum { kPrepassZClass = 0, kPrepassPlanes = 1, kPrepassIdle = 2 };
+struct PrepassRole {
+  int role;   // kPrepassZClass: the whole block sorts `bag`; kPrepassPlanes: this wave builds
+              // group g of side `zside` of `bag`; kPrepassIdle: a wave past the last group
+  int bag, g;
+  bool zside;
+  int64_t group;
+};
+TW_BITS_HD PrepassRole prepass_role(int64_t block, int wave, int64_t n_bags, int gx, int gz) {
+  if (block < n_bags) return PrepassRole{kPrepassZClass, (int)block, 0, false, 0};
+  const PlanesWave w = planes_wave((block - n_bags) * kPrepassWaves + wave, n_bags, gx, gz);
+  if (!w.active) return PrepassRole{kPrepassIdle, 0, 0, false, 0};
+  return PrepassRole{kPrepassPlanes, w.bag, w.g, w.zside, w.group};
+}
+
+// The z-class role keeps a bag of up to kPrepassCap images in registers, kPrepassPer per thread
+// (kPrepassPerSmall where the bag fits that), and reads it from global memory once; a larger
+// (or empty) bag runs the two-pass streaming loop.  An image's index inside its class is below
+// kPrepassCap: two of them share a register.
+constexpr int kPrepassPer = 64, kPrepassPerSmall = 16;
+constexpr int64_t kPrepassCap = (int64_t)kPrepassThreads * kPrepassPer;
+constexpr int64_t kPrepassCapSmall = (int64_t)kPrepassThreads * kPrepassPerSmall;
+static_assert(kPrepassCap <= (1 << 16), "two 16-bit class indices per register");
+// images per thread a bag of nz images is sorted with; 0: the streaming loop
+TW_BITS_HD int prepass_per_thread(int64_t nz) {
+  return nz < 1 || nz > kPrepassCap ? 0 : nz <= kPrepassCapSmall ? kPrepassPerSmall : kPrepassPer;
+}
+// The form a launch runs (tw_count_chain_prepass_of): 1 the separate launches, 2 fused with
+// every bag register-resident, 3 fused with bags that may take the streaming loop.
+// mode: tw_count_chain_prepass' setting (0 automatic: fused wherever the class form runs)
+TW_BITS_HD int prepass_form(int mode, int k, int64_t max_nz) {
+  if (k <= 0 || mode == 1) return 1;
+  return max_nz <= kPrepassCap ? 2 : 3;
 }
 
 #if defined(__HIPCC__)
