@@ -1501,6 +1501,62 @@ int tw_hsic_perm_sums(const double* d_held, int32_t d_h, const double* d_moved, 
                       const double* d_rows_moved, int32_t kern, double c_held, double c_moved,
                       int32_t wgs, void* d_work, double* d_out, void* stream);
 
+/* ---- Exact order statistics of pairwise squared distances (csrc/distselect.hip;
+ * tuplewise.bandwidth; an extension): the pieces of a radix select over the bit
+ * patterns of D, the squared distance of the triplet section (csrc/tripdist.h, the same device
+ * functions, so a D has the bits every other entry gives it).  The pair sets:
+ *   TW_DIST_WITHIN  the pairs i < j of d_x, (n, d) float64 row-major; d_z and m are ignored
+ *   TW_DIST_CROSS   all (x_i, z_k) of d_x (n, d) and d_z (m, d)
+ * 1 <= d <= 64, 0 <= n, m < 2^31.  The key of a pair is the 64-bit pattern of D.  For finite rows D
+ * is never NaN and never -0 (it may be +inf by overflow, the largest key), bit 63 is 0 and keys
+ * order as D does; rows with a non-finite entry are the caller's to refuse.
+ *
+ * A prefix group g is (prefix[g], prefix_bits[g]), 0 <= prefix_bits <= 63: a key belongs to it iff
+ * its bits 62 .. 63 - prefix_bits[g], read as a number, equal prefix[g] (prefix_bits = 0 and
+ * prefix = 0: every key).  `prefix` and `prefix_bits` are HOST arrays of n_groups entries, 1 <=
+ * n_groups <= tw_dist_select_max_groups() (8); they are read before the call returns.  A digit is
+ * bits [digit_shift, digit_shift + digit_bits) of a key, 1 <= digit_bits <=
+ * tw_dist_select_digit_bits() (11), digit_shift + digit_bits <= 63.
+ *
+ * tw_dist_hist: d_hist is n_groups rows of 2^tw_dist_select_digit_bits() uint64 bins
+ * (tw_dist_hist_bytes(n_groups) bytes, 0 for a refused n_groups); the call zeroes it, then
+ *   d_hist[g * 2^bits + digit(key)] += 1   for every pair of the set and every group g the key
+ *                                          belongs to
+ * Each pair is visited once (tile pairs of tw_mmd_tile() rows a side as in tw_mmd_sums; a diagonal
+ * tile counts anchor > point only) and the tile, tail and diagonal masks predicate the update: a
+ * masked pair touches no bin.  Counts are integers added by integer atomics (uint32 bins per
+ * workgroup in LDS, which a workgroup's 32768 pairs cannot overflow, then uint64 adds), so the
+ * histogram is exact and run-to-run identical.
+ *
+ * tw_dist_gather: the same walk; every key that belongs to at least one group is written once to
+ * d_keys (capacity entries) in an unspecified order.  d_count[0] = the number of such keys,
+ * whatever the capacity; d_count[1] = 1 iff it exceeds the capacity, and then the keys past it are
+ * dropped, never written.  The call zeroes d_count (2 entries).
+ *
+ * tw_keys_hist: tw_dist_hist's histogram of the n_keys entries of a key buffer.
+ *
+ * None of the three needs scratch.  TW_ERR_ARG before any device work: a null pointer (d_z for
+ * TW_DIST_WITHIN and d_keys at capacity 0 may be NULL), an unknown pair set, d outside [1, 64], a
+ * size outside [0, 2^31), n_groups outside [1, 8], prefix bits outside [0, 63] or a prefix wider
+ * than them, a digit outside the limits above, a negative capacity or n_keys, a grid past 2^31
+ * workgroups. */
+#define TW_DIST_WITHIN 0
+#define TW_DIST_CROSS 1
+int32_t tw_dist_select_digit_bits(void);
+int32_t tw_dist_select_max_groups(void);
+int64_t tw_dist_hist_bytes(int32_t n_groups);
+int tw_dist_hist(const double* d_x, int64_t n, const double* d_z, int64_t m, int32_t d,
+                 int32_t pairs, const uint64_t* prefix, const int32_t* prefix_bits,
+                 int32_t n_groups, int32_t digit_shift, int32_t digit_bits, uint64_t* d_hist,
+                 void* stream);
+int tw_dist_gather(const double* d_x, int64_t n, const double* d_z, int64_t m, int32_t d,
+                   int32_t pairs, const uint64_t* prefix, const int32_t* prefix_bits,
+                   int32_t n_groups, uint64_t* d_keys, int64_t capacity, uint64_t* d_count,
+                   void* stream);
+int tw_keys_hist(const uint64_t* d_keys, int64_t n_keys, const uint64_t* prefix,
+                 const int32_t* prefix_bits, int32_t n_groups, int32_t digit_shift,
+                 int32_t digit_bits, uint64_t* d_hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

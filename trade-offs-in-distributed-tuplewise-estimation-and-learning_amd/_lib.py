@@ -26,6 +26,7 @@ TW_LOSS_HINGE, TW_LOSS_LOGISTIC = 0, 1
 TW_SELF_GINI, TW_SELF_VAR, TW_SELF_KENDALL = 0, 1, 2
 TW_MMD_GAUSSIAN, TW_MMD_ENERGY = 0, 1
 TW_HSIC_GAUSSIAN, TW_HSIC_DISTANCE = 0, 1
+TW_DIST_WITHIN, TW_DIST_CROSS = 0, 1
 
 _vp, _i64, _i32, _u64, _f64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                ctypes.c_uint64, ctypes.c_double)
@@ -290,6 +291,12 @@ _SIGNATURES = {
     "tw_hsic_perm_work_bytes": [_i64, _i32, _i32],
     "tw_hsic_perm_sums": [_vp, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _f64, _f64, _i32,
                           _vp, _vp, _vp],
+    "tw_dist_select_digit_bits": [],
+    "tw_dist_select_max_groups": [],
+    "tw_dist_hist_bytes": [_i32],
+    "tw_dist_hist": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "tw_dist_gather": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp],
+    "tw_keys_hist": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -320,6 +327,7 @@ _RESTYPES = {
     "tw_hsic_work_bytes": ctypes.c_int64,
     "tw_hsic_idx_work_bytes": ctypes.c_int64,
     "tw_hsic_perm_work_bytes": ctypes.c_int64,
+    "tw_dist_hist_bytes": ctypes.c_int64,
 }
 
 _lib = None

@@ -11,7 +11,8 @@ g the pair function of tuplewise.mmd:
 
     kernel="gaussian"  K_ij = exp(c_x * D(x_i, x_j)), L_ij = exp(c_y * D(y_i, y_j)), c = -1.0 /
                        (2.0 * sigma * sigma) computed here in Python floats; sigma is required: a
-                       positive finite scalar for both sides or a pair (sigma_x, sigma_y)
+                       positive finite scalar for both sides or a pair (sigma_x, sigma_y); either
+                       may be the string "median" (below)
     kernel="distance"  K_ij = sqrt(D(x_i, x_j)), L_ij = sqrt(D(y_i, y_j)); sigma must be None
 
 with zero diagonals.  The device reduces (csrc/hsic.hip): every unordered pair
@@ -36,6 +37,15 @@ tuplewise.mmd for the proportional partition without replacement: the host owns 
 the draws (NumPy's global legacy RNG, in NumPy's order), the device the arithmetic.
 
 The permutation test that judges Un is its own module, tuplewise.hsic_perm.
+
+sigma="median" is the median heuristic PER SIDE: sigma_x is the median Euclidean distance over the
+pairs i < j of X and sigma_y that of Y, exact (tuplewise.bandwidth.median_distance(X), DESIGN.md
+§4.16); a pair may mix, e.g. ("median", 2.0).  It is resolved ONCE per public call, after every
+argument check and before the shuffle or the first draw, and the numbers are passed down: a side's
+median does not change when the rows are permuted, so the reshuffled estimators (UnNT, UnNBT) use
+one value and the RNG is consumed exactly as with those numbers.  With "median" a non-finite entry
+on that side is a ValueError (with a numeric sigma a NaN propagates into the sums instead), and so
+is a median of 0; with the distance kernel "median" is a ValueError like any other sigma.
 """
 from __future__ import annotations
 
@@ -67,7 +77,13 @@ class Components(NamedTuple):
 
 
 # ------------------------------------------------------------------------------ host checks
+def _is_median(sigma) -> bool:
+    return isinstance(sigma, str) and sigma == "median"
+
+
 def _one_coef(sigma):
+    if _is_median(sigma):
+        return None  # resolved by _resolve once the rows are checked
     try:
         sigma = float(sigma)
     except (TypeError, ValueError):
@@ -81,7 +97,8 @@ def _one_coef(sigma):
 
 def _coef(kernel, sigma):
     """(kernel id, c_x, c_y) or a ValueError: c = -1 / (2 sigma^2) per side for the Gaussian
-    kernel, 0.0 (unused) for the distance kernel."""
+    kernel, 0.0 (unused) for the distance kernel; a side's c is None for "median", which _resolve
+    turns into a number."""
     if kernel not in _KERNELS:
         raise ValueError(f"kernel={kernel!r} is not one of {list(_KERNELS)}")
     if kernel == "distance":
@@ -113,6 +130,33 @@ def _check(X, Y, kernel, sigma):
     if Xf.shape[0] >= 2 ** 31:
         raise ValueError("at most 2^31 - 1 rows")
     return Xf, Yf, kid, cx, cy
+
+
+def _resolve(Xf, Yf, sigma, cx, cy):
+    """(sigma, c_x, c_y) as numbers: a side given as "median" (its c is None) gets the median
+    distance over the pairs of that side's rows — device work, so callers finish their argument
+    checks first and call this once, before any shuffle or draw.  With no such side everything is
+    returned as it is."""
+    if cx is not None and cy is not None:
+        return sigma, cx, cy
+    from . import bandwidth
+    _median_sigma = bandwidth._median_sigma
+    sx, sy = sigma if isinstance(sigma, (tuple, list, np.ndarray)) else (sigma, sigma)
+    for A, name, c in ((Xf, "X", cx), (Yf, "Y", cy)):  # both sides' rows before any device work
+        if c is None:
+            bandwidth._check_finite(A, name)
+    if cx is None:
+        sx = _median_sigma(Xf, None, "within", "X")
+    if cy is None:
+        sy = _median_sigma(Yf, None, "within", "Y")
+    return (sx, sy), _one_coef(sx), _one_coef(sy)
+
+
+def _checked(X, Y, kernel, sigma):
+    """_check and _resolve: for the calls whose every argument check is _check's."""
+    Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
+    sigma, cx, cy = _resolve(Xf, Yf, sigma, cx, cy)
+    return Xf, Yf, kid, cx, cy, sigma
 
 
 def _u(s, ra, rb, rab, n: int) -> float:
@@ -186,21 +230,21 @@ def _sums_indexed(Xf, Yf, ii, jj, qq, rr, quad_off, kid, cx, cy):
 # ------------------------------------------------------------------------------- estimators
 def components(X, Y, kernel="gaussian", sigma=None):
     """The eight sums S_KL, S_KK, S_LL, R_K, R_L, R_KL, R_KK, R_LL of the whole sample."""
-    Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
+    Xf, Yf, kid, cx, cy, _ = _checked(X, Y, kernel, sigma)
     s = _sums_blocks(Xf, Yf, [0, Xf.shape[0]], kid, cx, cy)[0][0]
     return Components(*(np.float64(v) for v in s))
 
 
 def row_sums(X, Y, kernel="gaussian", sigma=None):
     """(k, l): the (n,) float64 row sums k_i = sum_j K_ij and l_i = sum_j L_ij."""
-    Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
+    Xf, Yf, kid, cx, cy, _ = _checked(X, Y, kernel, sigma)
     rows = _sums_blocks(Xf, Yf, [0, Xf.shape[0]], kid, cx, cy, want_rows=True)[1]
     return rows[:, 0].copy(), rows[:, 1].copy()
 
 
 def Un(X, Y, kernel="gaussian", sigma=None):
     """The complete statistic: HSIC_u (Gaussian) or the unbiased squared distance covariance."""
-    Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
+    Xf, Yf, kid, cx, cy, _ = _checked(X, Y, kernel, sigma)
     s = _sums_blocks(Xf, Yf, [0, Xf.shape[0]], kid, cx, cy)[0][0]
     return _value(s, Xf.shape[0])
 
@@ -208,7 +252,7 @@ def Un(X, Y, kernel="gaussian", sigma=None):
 def correlation(X, Y, kernel="gaussian", sigma=None):
     """Un / sqrt(Un(X, X) Un(Y, Y)): the unbiased CKA (Gaussian) or the bias-corrected squared
     distance correlation; NaN if the product of the two self terms is not > 0."""
-    Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
+    Xf, Yf, kid, cx, cy, _ = _checked(X, Y, kernel, sigma)
     s = _sums_blocks(Xf, Yf, [0, Xf.shape[0]], kid, cx, cy)[0][0]
     return _corr(s, Xf.shape[0])
 
@@ -227,6 +271,7 @@ def UB_indices(X, Y, i, j, q, r, kernel="gaussian", sigma=None):
     if (np.any(i == j) or np.any(i == q) or np.any(i == r) or np.any(j == q) or np.any(j == r)
             or np.any(q == r)):
         raise ValueError("a 4-tuple needs four distinct rows")
+    _, cx, cy = _resolve(Xf, Yf, sigma, cx, cy)
     if i.size == 0:
         return np.float64("nan")  # the mean of no terms
     s = _sums_indexed(Xf, Yf, i, j, q, r, [0, i.size], kid, cx, cy)[0]
@@ -260,7 +305,7 @@ def _draw_tuples(n: int, B: int):
 
 def UB(X, Y, B, kernel="gaussian", sigma=None):
     """The incomplete statistic: B 4-tuples drawn with replacement."""
-    Xf, Yf, _, _, _ = _check(X, Y, kernel, sigma)
+    Xf, Yf, _, _, _, sigma = _checked(X, Y, kernel, sigma)
     i, j, q, r = _draw_tuples(Xf.shape[0], int(B))
     return UB_indices(Xf, Yf, i, j, q, r, kernel, sigma)
 
@@ -309,19 +354,15 @@ def _block_fn(spec, fn):
     return fn
 
 
-def UN(X, Y, N, f_block, sampling_type="prop-SWOR"):
-    """Draws perm = np.random.permutation(n) once and applies it in place to BOTH arrays (X[:] =
-    X[perm]; Y[:] = Y[perm]: the pairing survives), cuts N blocks of k = int(n / N) >= 4 rows
-    (the remainder is left out) and averages f_block(x, y) over them.  Block functions made by
-    this module (the closures of UnN / UnNB) are evaluated together on the device; any other
-    callable is called block by block."""
+def _partition(X, Y, N, sampling_type, complete):
+    """UN's argument checks: (Xf, Yf, k) or a ValueError, before the draw.  complete: the blocks
+    go through tw_hsic_sums, which refuses some shapes."""
     if sampling_type != "prop-SWOR":
         raise ValueError(f"sampling_type={sampling_type!r}: only the proportional partition "
                          f"without replacement ('prop-SWOR') is offered for HSIC; 'SWOR' and "
                          f"'prop-SWR' are out of scope (DESIGN.md §4.14)")
     if not isinstance(X, np.ndarray) or not isinstance(Y, np.ndarray):
         raise ValueError("UN shuffles the caller's NumPy arrays in place")
-    spec = getattr(f_block, "_tw_hsic_block", None)
     Xf, Yf, _, _, _ = _check(X, Y, "distance", None)
     n = Xf.shape[0]
     try:
@@ -330,8 +371,34 @@ def UN(X, Y, N, f_block, sampling_type="prop-SWOR"):
         raise ValueError(f"N = {N!r} is not a number of blocks") from None
     if N < 1 or k < MIN_N:
         raise ValueError(f"N = {N} blocks of {k} row(s): a block needs at least {MIN_N} rows")
-    if hasattr(spec, "precheck"):
-        spec.precheck(k, N)  # a refused shape: a ValueError before the draw
+    if complete:
+        _work_bytes(N, k)  # a refused shape: a ValueError before the draw
+    return Xf, Yf, k
+
+
+def _resolve_blocks(X, Y, N, sampling_type, kernel, sigma, complete):
+    """sigma of a block estimator as numbers: where a side is "median", every check of the call
+    (the rows, then UN's partition) runs first, then each such side's median is taken once.  Any
+    other sigma is returned as it is, with nothing checked here."""
+    if not (_is_median(sigma) or (isinstance(sigma, (tuple, list))
+                                  and any(_is_median(s) for s in sigma))):
+        return sigma
+    Xf, Yf, _, cx, cy = _check(X, Y, kernel, sigma)
+    if cx is not None and cy is not None:
+        return sigma
+    _partition(X, Y, N, sampling_type, complete)
+    return _resolve(Xf, Yf, sigma, cx, cy)[0]
+
+
+def UN(X, Y, N, f_block, sampling_type="prop-SWOR"):
+    """Draws perm = np.random.permutation(n) once and applies it in place to BOTH arrays (X[:] =
+    X[perm]; Y[:] = Y[perm]: the pairing survives), cuts N blocks of k = int(n / N) >= 4 rows
+    (the remainder is left out) and averages f_block(x, y) over them.  Block functions made by
+    this module (the closures of UnN / UnNB) are evaluated together on the device; any other
+    callable is called block by block."""
+    spec = getattr(f_block, "_tw_hsic_block", None)
+    Xf, Yf, k = _partition(X, Y, N, sampling_type, hasattr(spec, "precheck"))
+    n = Xf.shape[0]
     perm = np.random.permutation(n)
     X[:] = X[perm]
     Y[:] = Y[perm]
@@ -342,6 +409,7 @@ def UN(X, Y, N, f_block, sampling_type="prop-SWOR"):
 
 def UnN(X, Y, N, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Block-wise complete statistic."""
+    sigma = _resolve_blocks(X, Y, N, sampling_type, kernel, sigma, True)
 
     def fun_block(x, y):
         return Un(x, y, kernel=kernel, sigma=sigma)
@@ -352,6 +420,7 @@ def UnN(X, Y, N, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
 
 def UnNB(X, Y, N, B, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Block-wise incomplete statistic."""
+    sigma = _resolve_blocks(X, Y, N, sampling_type, kernel, sigma, False)
 
     def fun_block(x, y):
         return UB(x, y, B, kernel=kernel, sigma=sigma)
@@ -362,9 +431,11 @@ def UnNB(X, Y, N, B, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
 
 def UnNT(X, Y, N, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Reshuffled block-wise complete statistic."""
+    sigma = _resolve_blocks(X, Y, N, sampling_type, kernel, sigma, True)  # once for all T
     return np.mean([UnN(X, Y, N, sampling_type, kernel, sigma) for _ in range(T)])
 
 
 def UnNBT(X, Y, N, B, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Reshuffled block-wise incomplete statistic."""
+    sigma = _resolve_blocks(X, Y, N, sampling_type, kernel, sigma, False)  # once for all T
     return np.mean([UnNB(X, Y, N, B, sampling_type, kernel, sigma) for _ in range(T)])

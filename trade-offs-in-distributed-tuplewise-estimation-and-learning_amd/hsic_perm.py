@@ -12,6 +12,13 @@ permutation on gathered rows; the row sums k, l and R_K, R_L come from one tw_hs
 the unpermuted sample, and the value of a permutation is hsic's U(S_p, R_K, R_L, Rab_p) in Python
 floats.  The host owns the draws (NumPy's global legacy RNG, in NumPy's order), the device the
 arithmetic.  (tuplewise.hsic itself keeps its surface: this module adds to it, as a sibling.)
+
+sigma="median" (for both sides, or inside a pair such as ("median", 2.0)) is tuplewise.hsic's: each
+such side's exact median distance over the pairs of its own rows, resolved once per call after
+every argument check and before the first draw.  A permutation of the pairing reorders one side's
+rows and leaves both medians as they are, so the observed column and every null column use the same
+two bandwidths.  With "median" a non-finite entry on that side is a ValueError (with a numeric sigma
+a NaN propagates instead), and so is a median of 0.
 """
 from __future__ import annotations
 
@@ -20,7 +27,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib as L
-from .hsic import _check, _u, _work_bytes
+from .hsic import _check, _resolve, _u, _work_bytes
 
 
 class PermutationResult(NamedTuple):
@@ -95,6 +102,7 @@ def permutation_sums(X, Y, perms, kernel="gaussian", sigma=None):
     device work).  The device path of permutation_test with nothing drawn: one upload."""
     Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
     perms = _check_perms(perms, Xf.shape[0])
+    _, cx, cy = _resolve(Xf, Yf, sigma, cx, cy)
     return _perm_sums(Xf, Yf, perms, kid, cx, cy)[0]
 
 
@@ -118,6 +126,7 @@ def permutation_test(X, Y, n_perm, kernel="gaussian", sigma=None):
     Xf, Yf, kid, cx, cy = _check(X, Y, kernel, sigma)
     n = Xf.shape[0]
     _work_bytes(1, n)  # a refused shape: a ValueError before the draws
+    _, cx, cy = _resolve(Xf, Yf, sigma, cx, cy)  # a "median" side: once, before any draw
     L.device()  # no HIP device: the package's RuntimeError, before any draw
     perms = np.empty((n_perm + 1, n), dtype=np.int32)
     perms[0] = np.arange(n, dtype=np.int32)

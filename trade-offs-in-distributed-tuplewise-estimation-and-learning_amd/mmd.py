@@ -12,7 +12,7 @@ D(a, b) is the squared Euclidean distance of tuplewise.triplets, in its arithmet
 D(a, a) = 0 exactly and D(a, b) = D(b, a) bit for bit.  The pair function:
 
     kernel="gaussian"  g = exp(c * D), c = -1.0 / (2.0 * sigma * sigma) computed here in Python
-                       floats; sigma is required, positive and finite
+                       floats; sigma is required: positive and finite, or the string "median"
     kernel="energy"    g = sqrt(D); sigma must be None
 
 The device reduces (csrc/mmd.hip): per block three doubles leave the chip,
@@ -38,6 +38,16 @@ anywhere in the pooled sample makes all three sums of every column NaN (0 * inf 
 products, inf - inf in the identities): permutation_test then returns a NaN statistic, an all-NaN
 null and pvalue = 1 / (n_perm + 1).  Under the Gaussian kernel a pair with D = +inf is a term of
 exactly 0 and every column is finite.
+
+sigma="median" is the median heuristic: the median Euclidean distance over the pairs of the POOLED
+sample [X; Z], exact (tuplewise.bandwidth.median_distance(X, Z, pairs="pooled")).
+It is resolved ONCE per public call, after every argument check and before the first shuffle or
+draw, and the number is passed down: the pooled median does not change under the shuffles of the
+block estimators or under the relabellings of the permutation test, so the reshuffled estimators
+(UnNT, UnNBT) and every null column use the same value, and the RNG is consumed exactly as with
+that number.  With sigma="median" a non-finite entry in X or Z is a ValueError (with a numeric
+sigma a NaN propagates into the sums instead), and so is a median of 0; with the energy kernel
+"median" is a ValueError like any other sigma.
 """
 from __future__ import annotations
 
@@ -56,9 +66,13 @@ MAX_D = 64
 
 
 # ------------------------------------------------------------------------------ host checks
+def _is_median(sigma) -> bool:
+    return isinstance(sigma, str) and sigma == "median"
+
+
 def _coef(kernel, sigma):
     """(kernel id, c) or a ValueError: c = -1 / (2 sigma^2) for the Gaussian kernel, 0.0 (unused)
-    for the energy kernel."""
+    for the energy kernel; c is None for sigma="median", which _resolve turns into a number."""
     if kernel not in _KERNELS:
         raise ValueError(f"kernel={kernel!r} is not one of {list(_KERNELS)}")
     if kernel == "energy":
@@ -67,6 +81,8 @@ def _coef(kernel, sigma):
         return _KERNELS[kernel], 0.0
     if sigma is None:
         raise ValueError("the Gaussian kernel needs sigma")
+    if _is_median(sigma):
+        return _KERNELS[kernel], None  # resolved by _resolve once the rows are checked
     try:
         sigma = float(sigma)
     except (TypeError, ValueError):
@@ -94,6 +110,17 @@ def _check(X, Z, kernel, sigma):
     if max(Xf.shape[0], Zf.shape[0]) >= 2 ** 31:
         raise ValueError("at most 2^31 - 1 rows per sample")
     return Xf, Zf, kid, c
+
+
+def _resolve(Xf, Zf, kernel, sigma, c):
+    """(sigma, c) as numbers: sigma="median" (c is None) becomes the pooled median distance of the
+    checked rows — device work, so callers finish their argument checks first and call this once,
+    before any shuffle or draw.  Any other sigma is returned as it is."""
+    if c is not None:
+        return sigma, c
+    from .bandwidth import _median_sigma
+    sigma = _median_sigma(Xf, Zf, "pooled", "the pooled sample")
+    return sigma, _coef(kernel, sigma)[1]
 
 
 def _value(sxx, szz, sxz, n: int, m: int, kid: int) -> np.float64:
@@ -145,6 +172,7 @@ def _sums_indexed(Xf, Zf, ii, jj, kk, ll, quad_off, kid, c):
 def components(X, Z, kernel="gaussian", sigma=None):
     """(Sxx, Szz, Sxz): the three sums of g over the pairs of X, the pairs of Z and all (x, z)."""
     Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    _, c = _resolve(Xf, Zf, kernel, sigma, c)
     s = _sums_blocks(Xf, Zf, [0, Xf.shape[0]], [0, Zf.shape[0]], kid, c)[0]
     return np.float64(s[0]), np.float64(s[1]), np.float64(s[2])
 
@@ -152,6 +180,7 @@ def components(X, Z, kernel="gaussian", sigma=None):
 def Un(X, Z, kernel="gaussian", sigma=None):
     """The complete statistic: MMD^2_u (Gaussian) or the energy distance."""
     Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    _, c = _resolve(Xf, Zf, kernel, sigma, c)
     sxx, szz, sxz = _sums_blocks(Xf, Zf, [0, Xf.shape[0]], [0, Zf.shape[0]], kid, c)[0]
     return _value(sxx, szz, sxz, Xf.shape[0], Zf.shape[0], kid)
 
@@ -169,6 +198,7 @@ def UB_indices(X, Z, i, j, k, l, kernel="gaussian", sigma=None):  # noqa: E741
     i, j, k, l = (a.reshape(-1) for a in (i, j, k, l))  # noqa: E741
     if np.any(i == j) or np.any(k == l):  # (rows as _check_index returns them, >= 0)
         raise ValueError("a quadruple needs i != j and k != l")
+    _, c = _resolve(Xf, Zf, kernel, sigma, c)
     if i.size == 0:
         return np.float64("nan")  # the mean of no terms
     s = _sums_indexed(Xf, Zf, i, j, k, l, [0, i.size], kid, c)[0]
@@ -195,7 +225,8 @@ def _draw_quadruples(n: int, m: int, B: int):
 
 def UB(X, Z, B, kernel="gaussian", sigma=None):
     """The incomplete statistic: B quadruples drawn with replacement."""
-    Xf, Zf, _, _ = _check(X, Z, kernel, sigma)
+    Xf, Zf, _, c = _check(X, Z, kernel, sigma)
+    sigma, _ = _resolve(Xf, Zf, kernel, sigma, c)
     i, j, k, l = _draw_quadruples(Xf.shape[0], Zf.shape[0], int(B))  # noqa: E741
     return UB_indices(Xf, Zf, i, j, k, l, kernel, sigma)
 
@@ -245,23 +276,42 @@ def _block_fn(spec, fn):
     return fn
 
 
-def UN(X, Z, N, f_block, sampling_type="prop-SWOR"):
-    """Shuffles X, then Z, in place (rows), cuts N blocks of k = int(n / N) rows of X and
-    kz = int(m / N) rows of Z (the remainders are left out) and averages f_block(x, z) over
-    them.  Block functions made by this module (the closures of UnN / UnNB) are evaluated
-    together on the device; any other callable is called block by block."""
+def _partition(X, Z, N, sampling_type):
+    """UN's argument checks: (Xf, Zf, k, kz) or a ValueError, before any shuffle."""
     if sampling_type != "prop-SWOR":
         raise ValueError(f"sampling_type={sampling_type!r}: only the proportional partition "
                          f"without replacement ('prop-SWOR') is offered for the MMD; 'SWOR' and "
                          f"'prop-SWR' are out of scope (DESIGN.md §4.12)")
     if not isinstance(X, np.ndarray) or not isinstance(Z, np.ndarray):
         raise ValueError("UN shuffles the caller's NumPy arrays in place")
-    spec = getattr(f_block, "_tw_mmd_block", None)
     Xf, Zf, _, _ = _check(X, Z, "energy", None)
     k, kz = int(Xf.shape[0] / N), int(Zf.shape[0] / N)
     if k < 2 or kz < 2:
         raise ValueError(f"N = {N} blocks of {k} row(s) of X and {kz} of Z: a block needs at "
                          f"least 2 rows of each sample")
+    return Xf, Zf, k, kz
+
+
+def _resolve_blocks(X, Z, N, sampling_type, kernel, sigma):
+    """sigma of a block estimator as a number: for sigma="median" every check of the call (the
+    rows, then UN's partition) runs first, then the median is taken once.  Any other sigma is
+    returned as it is, with nothing checked here."""
+    if not _is_median(sigma):
+        return sigma
+    Xf, Zf, _, c = _check(X, Z, kernel, sigma)
+    if c is not None:
+        return sigma
+    _partition(X, Z, N, sampling_type)
+    return _resolve(Xf, Zf, kernel, sigma, c)[0]
+
+
+def UN(X, Z, N, f_block, sampling_type="prop-SWOR"):
+    """Shuffles X, then Z, in place (rows), cuts N blocks of k = int(n / N) rows of X and
+    kz = int(m / N) rows of Z (the remainders are left out) and averages f_block(x, z) over
+    them.  Block functions made by this module (the closures of UnN / UnNB) are evaluated
+    together on the device; any other callable is called block by block."""
+    Xf, Zf, k, kz = _partition(X, Z, N, sampling_type)
+    spec = getattr(f_block, "_tw_mmd_block", None)
     np.random.shuffle(X)
     np.random.shuffle(Z)
     if spec is not None:
@@ -271,6 +321,7 @@ def UN(X, Z, N, f_block, sampling_type="prop-SWOR"):
 
 def UnN(X, Z, N, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Block-wise complete statistic."""
+    sigma = _resolve_blocks(X, Z, N, sampling_type, kernel, sigma)
 
     def fun_block(x, z):
         return Un(x, z, kernel=kernel, sigma=sigma)
@@ -281,6 +332,7 @@ def UnN(X, Z, N, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
 
 def UnNB(X, Z, N, B, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Block-wise incomplete statistic."""
+    sigma = _resolve_blocks(X, Z, N, sampling_type, kernel, sigma)
 
     def fun_block(x, z):
         return UB(x, z, B, kernel=kernel, sigma=sigma)
@@ -291,11 +343,13 @@ def UnNB(X, Z, N, B, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
 
 def UnNT(X, Z, N, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Reshuffled block-wise complete statistic."""
+    sigma = _resolve_blocks(X, Z, N, sampling_type, kernel, sigma)  # once, not per repetition
     return np.mean([UnN(X, Z, N, sampling_type, kernel, sigma) for _ in range(T)])
 
 
 def UnNBT(X, Z, N, B, T, sampling_type="prop-SWOR", kernel="gaussian", sigma=None):
     """Reshuffled block-wise incomplete statistic."""
+    sigma = _resolve_blocks(X, Z, N, sampling_type, kernel, sigma)  # once, not per repetition
     return np.mean([UnNB(X, Z, N, B, sampling_type, kernel, sigma) for _ in range(T)])
 
 
@@ -348,6 +402,7 @@ def permutation_sums(X, Z, labels, kernel="gaussian", sigma=None):
     one upload and one launch."""
     Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
     labels = _check_labels(labels, Xf.shape[0], Xf.shape[0] + Zf.shape[0])
+    _, c = _resolve(Xf, Zf, kernel, sigma, c)
     return _perm_sums(Xf, Zf, labels, kid, c)
 
 
@@ -367,6 +422,7 @@ def permutation_test(X, Z, n_perm, kernel="gaussian", sigma=None):
     if n_perm >= 2 ** 31 - 1:
         raise ValueError("at most 2^31 - 2 permutations")
     Xf, Zf, kid, c = _check(X, Z, kernel, sigma)
+    _, c = _resolve(Xf, Zf, kernel, sigma, c)  # sigma="median": once, before any draw
     L.device()  # no HIP device: the package's RuntimeError, before any draw
     n, m = Xf.shape[0], Zf.shape[0]
     labels = np.zeros((n_perm + 1, n + m), dtype=np.bool_)
