@@ -1393,6 +1393,38 @@ int tw_mmd_perm_sums(const double* d_w, int64_t n_rows, int32_t d, const uint32_
                      int32_t n_perm, int32_t kern, double c, void* d_work, double* d_out,
                      void* stream);
 
+/* ---- The row sums of the statistics above, for a grid of bandwidths (csrc/mmd_rows.hip;
+ * tuplewise.mmd_var; an extension): the partition, d, D, g and kern are
+ * tw_mmd_sums'; d_c holds n_sigma coefficients c_s = -1 / (2 sigma_s^2) in DEVICE memory (under
+ * TW_MMD_ENERGY n_sigma is 1 and d_c is not read).  With nx = d_blk_x_off[n_blocks] and nz =
+ * d_blk_z_off[n_blocks] the rows the offsets span, every row i of X and k of Z that belongs to a
+ * block gets, for every s,
+ *   d_rows_x[(s * nx + i) * 2 + 0] = sum over j != i of the block's X of g_s(x_i, x_j)
+ *   d_rows_x[(s * nx + i) * 2 + 1] = sum over k of the block's Z of g_s(x_i, z_k)
+ *   d_rows_z[(s * nz + k) * 2 + 0] = sum over i of the block's X of g_s(x_i, z_k)
+ *   d_rows_z[(s * nz + k) * 2 + 1] = sum over l != k of the block's Z of g_s(z_k, z_l)
+ * (absolute rows; rows before the first block are not written; a block of fewer than 2 rows of a
+ * sample has zeros in the sums over that sample's pairs).  Each unordered pair is visited once:
+ * D is evaluated once per pair and g applied n_sigma times to the held D, so a term has the bits
+ * tw_mmd_sums gives it, exp(fl(c_s * D)).  A pair feeds its point's sum in a register and its
+ * anchor's through a cross-lane reduce-scatter; one partial per row, tile column and sigma goes to
+ * d_work (tw_mmd_rows_work_bytes bytes, nothing to zero) and a second kernel adds a row's
+ * partials in a fixed order of the columns.  No atomics; results are run-to-run deterministic, a
+ * block's rows are the same bits alone, beside other blocks and wherever the partition starts,
+ * and a sigma's rows do not depend on n_sigma, on its position s or on the other coefficients.
+ * The coefficients live on the device, so TW_MMD_KERN_CHECKS' test of c is the caller's.
+ *
+ * TW_ERR_ARG before any device work: a null pointer (d_c may be null for the energy kernel), d
+ * outside [1, 64], an unknown kernel id, n_sigma outside [1, tw_mmd_rows_max_sigma()] or != 1 for
+ * the energy kernel, a negative size, max_n or max_m >= 2^31, a grid past 2^31 workgroups,
+ * d_work past 1 GiB.  tw_mmd_rows_work_bytes is 0 for shapes tw_mmd_rows refuses. */
+int32_t tw_mmd_rows_max_sigma(void);
+int64_t tw_mmd_rows_work_bytes(int32_t n_blocks, int64_t max_n, int64_t max_m, int32_t n_sigma);
+int tw_mmd_rows(const double* d_x, const double* d_z, int32_t d, const int64_t* d_blk_x_off,
+                const int64_t* d_blk_z_off, int32_t n_blocks, int64_t max_n, int64_t max_m,
+                int32_t kern, const double* d_c, int32_t n_sigma, void* d_work, double* d_rows_x,
+                double* d_rows_z, void* stream);
+
 /* ---- Kernel independence U-statistics of degree 4 on one paired sample (csrc/hsic.hip;
  * tuplewise.hsic; an extension): the unbiased Hilbert-Schmidt independence
  * criterion HSIC_u (Song et al. 2012) and the unbiased squared distance covariance

@@ -280,6 +280,10 @@ _SIGNATURES = {
     "tw_mmd_perm_cols": [],
     "tw_mmd_perm_work_bytes": [_i64, _i32],
     "tw_mmd_perm_sums": [_vp, _i64, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _vp],
+    "tw_mmd_rows_max_sigma": [],
+    "tw_mmd_rows_work_bytes": [_i32, _i64, _i64, _i32],
+    "tw_mmd_rows": [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp,
+                    _vp],
     "tw_hsic_tile": [],
     "tw_hsic_work_bytes": [_i32, _i64, _i32],
     "tw_hsic_idx_work_bytes": [_i32, _i64],
@@ -324,6 +328,7 @@ _RESTYPES = {
     "tw_mmd_work_bytes": ctypes.c_int64,
     "tw_mmd_idx_work_bytes": ctypes.c_int64,
     "tw_mmd_perm_work_bytes": ctypes.c_int64,
+    "tw_mmd_rows_work_bytes": ctypes.c_int64,
     "tw_hsic_work_bytes": ctypes.c_int64,
     "tw_hsic_idx_work_bytes": ctypes.c_int64,
     "tw_hsic_perm_work_bytes": ctypes.c_int64,

@@ -30,7 +30,7 @@
 #include "selfreduce.h"
 #include "tripdist.h"
 #include "mmdtile.h"  // kMmdT, kMmdSA, mmd_g, mmd_load (shared with mmd.hip, mmd_perm.hip)
-#include "hsictile.h"  // kHsicTA, kHsicSA, hsic_stage, hsic_side, hsic_ok (shared with hsic_perm.hip)
+#include "hsictile.h"  // kHsicTA, kHsicSA, hsic_stage, hsic_side, hsic_ok, hsic_anchor_sums (shared)
 #include <algorithm>
 #include <cmath>
 
@@ -41,7 +41,6 @@ constexpr int kHsicRowsPerWg = kWave;                   // rows per workgroup of
 constexpr int kHsicQPT = 4;                             // 4-tuples per lane (tw_hsic_idx32)
 constexpr int64_t kHsicWorkBudget = 1ll << 30;          // bytes of d_work a launch may ask for
 constexpr int64_t kHsicMinWgs = 2 * 2 * 256;            // two rounds on 256 CUs x 2 workgroups
-static_assert(kHsicTA == 8 && kTripR == 2 && kWave == 64, "hsic_anchor_sums' butterfly");
 static_assert(kBlock / kWave * kMmdT * 2 <= kHsicSA * kTripMaxD, "the point scratch aliases sax");
 static_assert(2 * kMmdT == kBlock, "one thread per point and side in the point-side combine");
 
@@ -94,47 +93,8 @@ inline int64_t hsic_idx_blocks_per_shard(int64_t max_quads) {
   return std::max<int64_t>(1, ceil_div(max_quads, (int64_t)kBlock * kHsicQPT));
 }
 
-// v of lane (l ^ O) by a DPP lane move.
-template <int O>
-__device__ __forceinline__ double hsic_lane_xor(double v) {
-  static_assert(O == 1 || O == 2 || O == 8, "a DPP pattern");
-  if constexpr (O == 1) return dpp_f64<0xB1>(v);        // quad_perm [1,0,3,2]
-  else if constexpr (O == 2) return dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-  else return dpp_f64<0x128>(v);                        // row_ror:8
-}
-
-// One level of the reduce-scatter: lanes whose bit O is clear keep the lower half of the 2 N
-// values, the others the upper half, and each adds what its partner (lane ^ O) holds of them.
-template <int O, int N>
-__device__ __forceinline__ void hsic_halve(double (&v)[kHsicTA], bool up) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const double keep = up ? v[i + N] : v[i], send = up ? v[i] : v[i + N];
-    v[i] = keep + hsic_lane_xor<O>(send);
-  }
-}
-
-// v[a] = this lane's two points' terms of anchor a.  Returns, in every lane, the sum over the
-// wave's 128 points for anchor hsic_anchor_of(lane): 8 -> 4 -> 2 -> 1 values a lane over lane
-// bits 0, 1, 3 (DPP moves), then the lanes that hold the same anchor are added over bits 2, 4, 5.
-// A fixed order.
-__device__ __forceinline__ double hsic_anchor_sums(double (&v)[kHsicTA], int lane) {
-  hsic_halve<1, 4>(v, lane & 1);
-  hsic_halve<2, 2>(v, lane & 2);
-  hsic_halve<8, 1>(v, lane & 8);
-  double s = v[0];
-  s += __shfl_xor(s, 4, kWave);
-  s += __shfl_xor(s, 16, kWave);
-  s += __shfl_xor(s, 32, kWave);
-  return s;
-}
-__device__ __forceinline__ int hsic_anchor_of(int lane) {
-  return ((lane & 1) << 2) | (lane & 2) | ((lane & 8) >> 3);
-}
-__device__ __forceinline__ bool hsic_anchor_lane(int lane) { return (lane & ~0xB) == 0; }
-
-// (hsic_stage, hsic_side and hsic_ok are hsictile.h's.)  The fold runs one side at a time so that
-// only one side's distances are live beside the other's g values.
+// (hsic_stage, hsic_side, hsic_ok and the butterfly hsic_anchor_sums are hsictile.h's.)  The fold
+// runs one side at a time so that only one side's distances are live beside the other's g values.
 // The X side: ak becomes K (masked), S_KK, the lane's points' k terms, the anchors' terms vk.
 template <int K, bool MASK>
 __device__ __forceinline__ void hsic_fold_k(double (&ak)[kHsicTA][kTripR], double cx, int a_first,

@@ -56,4 +56,46 @@ __device__ __forceinline__ bool hsic_ok(int a, int r, int a_first, int na, int d
   return !MASK || (valid[r] && a_first + a < na && a_first + a + diag_shift > r * kWave + lane);
 }
 
+// The anchor side's cross-lane sums (hsic.hip, mmd_rows.hip).
+static_assert(kHsicTA == 8 && kTripR == 2 && kWave == 64, "hsic_anchor_sums' butterfly");
+
+// v of lane (l ^ O) by a DPP lane move.
+template <int O>
+__device__ __forceinline__ double hsic_lane_xor(double v) {
+  static_assert(O == 1 || O == 2 || O == 8, "a DPP pattern");
+  if constexpr (O == 1) return dpp_f64<0xB1>(v);        // quad_perm [1,0,3,2]
+  else if constexpr (O == 2) return dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+  else return dpp_f64<0x128>(v);                        // row_ror:8
+}
+
+// One level of the reduce-scatter: lanes whose bit O is clear keep the lower half of the 2 N
+// values, the others the upper half, and each adds what its partner (lane ^ O) holds of them.
+template <int O, int N>
+__device__ __forceinline__ void hsic_halve(double (&v)[kHsicTA], bool up) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const double keep = up ? v[i + N] : v[i], send = up ? v[i] : v[i + N];
+    v[i] = keep + hsic_lane_xor<O>(send);
+  }
+}
+
+// v[a] = this lane's two points' terms of anchor a.  Returns, in every lane, the sum over the
+// wave's 128 points for anchor hsic_anchor_of(lane): 8 -> 4 -> 2 -> 1 values a lane over lane
+// bits 0, 1, 3 (DPP moves), then the lanes that hold the same anchor are added over bits 2, 4, 5.
+// A fixed order.
+__device__ __forceinline__ double hsic_anchor_sums(double (&v)[kHsicTA], int lane) {
+  hsic_halve<1, 4>(v, lane & 1);
+  hsic_halve<2, 2>(v, lane & 2);
+  hsic_halve<8, 1>(v, lane & 8);
+  double s = v[0];
+  s += __shfl_xor(s, 4, kWave);
+  s += __shfl_xor(s, 16, kWave);
+  s += __shfl_xor(s, 32, kWave);
+  return s;
+}
+__device__ __forceinline__ int hsic_anchor_of(int lane) {
+  return ((lane & 1) << 2) | (lane & 2) | ((lane & 8) >> 3);
+}
+__device__ __forceinline__ bool hsic_anchor_lane(int lane) { return (lane & ~0xB) == 0; }
+
 }  // namespace tw
