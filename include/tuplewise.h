@@ -274,6 +274,20 @@ int32_t tw_count_chain_class_digits(int32_t w);
  * 4 where it runs the wide digits, 3 anywhere else (where the launch runs no digit loop — see
  * tw_count_chain_class_form — the setting has no effect). */
 int32_t tw_count_chain_class_digits_of(int32_t nb, int32_t k);
+/* A/B control of the class count's LDS-table form: where a launch would run the
+ * wide digits, one block of 16 waves per (bag, x tile of two groups) tabulates the carries of
+ * the low 8 planes in 128 KiB of LDS and its waves read them from there — 5 VALU per z image
+ * instead of 8.  0: the automatic rule (chainclass.h class_lds_runs); 1: off, every launch is
+ * the digit loops'; 2: on wherever the form fits (the wide digits would run, two groups per
+ * tile, no swapped items in the plan); -1 only reports.  Returns the setting in force before
+ * the call; any other value changes nothing and returns TW_ERR_ARG.  Process-global; same
+ * counts, same workspace: every launch re-encodes its z region for the loop it runs.
+ * tw_count_chain_class_span has no effect on a launch of this form. */
+int32_t tw_count_chain_class_lds(int32_t mode);
+/* 1 if a strict tw_count_pairs_chain_planes launch with these arguments runs the LDS-table form
+ * under the current settings, 0 if it runs any other. */
+int32_t tw_count_chain_class_lds_of(int32_t n_shards, int32_t steps, int64_t max_nx,
+                                    int64_t max_nz, int64_t image_bound);
 /* A/B control of how the class-run form's pre-passes are launched.  0 (automatic)
  * and 2: one launch (k_chain_prepass) builds the planes, sorts every bag's z images into class
  * runs — in registers, one pass over global memory, for bags of up to 16384 z images — and

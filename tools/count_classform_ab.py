@@ -16,7 +16,18 @@ pass: under the automatic class bits, swap rule and span, tw_count_chain_class_d
 forced to 3 (the four-digit loop), to 4 (the wide digits where NB - K = 12) and automatic,
 interleaved over the rounds; per shape the ratio of medians of the whole native call to the
 four-digit loop and the four-digit loop's own spread.  Shapes whose automatic class bits leave a
-low field other than 12 planes run the same kernel under every setting."""
+low field other than 12 planes run the same kernel under every setting.
+
+--lds [out.json]: the LDS-table sweep of DESIGN §4.1m, same shapes, one process per pass: under
+the automatic class bits, swap rule and digit width, tw_count_chain_class_lds at 1 (off: the
+digit loops), 2 (on wherever the form fits) and automatic, interleaved over the rounds; per
+shape the ratio of medians of the whole native call to off, off's own spread, the launch's
+(bag, x tile) blocks and whether each setting ran the form (tw_count_chain_class_lds_of).  The
+span and digit sweeps above run with the form off: they measure the loops they name.
+
+--lds-blocks [out.json]: the same three settings over launches of 128 .. 1024 (bag, tile)
+blocks (G = 4: 16 bags of 4 tiles per step, K = 2 .. 16 steps), around the whole multiples of
+the chip's 256 CUs: the form runs one block per CU at a time."""
 import json
 import os
 import pathlib
@@ -31,6 +42,8 @@ SPAN_SETTINGS = [("M=1", -1, 1, 1)] + [(f"M={m}", -1, 1, m) for m in (2, 4, 8, 1
     ("M=whole bag", -1, 1, WHOLE_BAG), ("automatic", -1, 1, 0)]
 # (name, class bits, swap, span, planes per digit)
 DIGIT_SETTINGS = [("digits=3", -1, 1, 0, 3), ("digits=4", -1, 1, 0, 4), ("automatic", -1, 1, 0, 0)]
+# (name, class bits, swap, span, planes per digit, tw_count_chain_class_lds)
+LDS_SETTINGS = [("lds=off", -1, 1, 0, 0, 1), ("lds=on", -1, 1, 0, 0, 2), ("automatic", -1, 1, 0, 0, 0)]
 # (name, G, K): G ranks share the strong problem; G = 0: C2; G = -1: 64 bags per step of
 # 7 * 2048 + 100 x images, a remainder small enough that class_swap_mode keeps it swapped
 SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1, 4),
@@ -38,7 +51,11 @@ SHAPES = [("headline K=20", 1, 20), ("headline K=32", 1, 32), ("headline K=4", 1
           ("G=8 K=20", 8, 20), ("C2", 0, 1), ("remainder 100 K=20", -1, 20)]
 
 
-def child(settings, base):
+# launches of 64 K (bag, tile) blocks
+BLOCK_SHAPES = [(f"G=4 K={K}", 4, K) for K in (2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 16)]
+
+
+def child(settings, base, shapes=None):
     sys.path.insert(0, str(ROOT))
     import numpy as np
     import torch
@@ -49,7 +66,7 @@ def child(settings, base):
 
     gen = torch.Generator(device="cuda").manual_seed(1)
     report = []
-    for name, G, K in SHAPES:
+    for name, G, K in shapes or SHAPES:
         if G == 0:  # C2: one bag of 1e5 x 1e5
             nl, Nl, bound = 100_000, 1, 100_000
         elif G < 0:
@@ -65,6 +82,7 @@ def child(settings, base):
         wb = int(L.lib().tw_chain_planes_work_bytes(Nl, K, k, kz, 0, bound))
         work = torch.empty(max(wb, 256), dtype=torch.uint8, device="cuda")
         ts = {s[0]: [] for s in settings}
+        form = {}
         ref = None
 
         def call():
@@ -74,9 +92,12 @@ def child(settings, base):
             for _ in range(ROUNDS):
                 for sname, bits, swap, span, *digits in settings:
                     assert L.lib().tw_count_chain_class_digits(digits[0] if digits else 0) != 1
+                    # (sweeps that do not name the LDS-table form run with it off)
+                    assert L.lib().tw_count_chain_class_lds(digits[1] if len(digits) > 1 else 1) >= 0
                     L.call("tw_count_chain_set_class_bits", bits)
                     L.call("tw_count_chain_set_swap", swap)
                     L.lib().tw_count_chain_class_span(span)
+                    form[sname] = int(L.lib().tw_count_chain_class_lds_of(Nl, K, k, kz, bound))
                     e0 = torch.cuda.Event(enable_timing=True)
                     e1 = torch.cuda.Event(enable_timing=True)
                     call()  # warm
@@ -93,9 +114,12 @@ def child(settings, base):
             L.call("tw_count_chain_set_swap", 1)
             L.lib().tw_count_chain_class_span(0)
             L.lib().tw_count_chain_class_digits(0)
+            L.lib().tw_count_chain_class_lds(0)
         ms = {s: {"median": float(np.median(t)), "min": float(min(t)), "max": float(max(t))}
               for s, t in ts.items()}
         report.append({"shape": name, "bags": K * Nl, "nx": k, "nz": kz, "ms": ms,
+                       "blocks of (bag, tile of 2 groups)": K * Nl * -(-(-(-k // 2048)) // 2),
+                       "runs the LDS-table form": form,
                        f"ratio to {base}": {s: ms[s]["median"] / ms[base]["median"] for s in ms},
                        f"spread of {base}": (ms[base]["max"] - ms[base]["min"]) / ms[base]["median"]})
     print(json.dumps(report))
@@ -140,6 +164,19 @@ if __name__ == "__main__":
                    "tw_count_pairs_chain_planes under tw_count_chain_class_digits 3, 4 and the "
                    "automatic rule (automatic class bits, swap and span): ms of the whole native "
                    "call and the ratio of medians to the four-digit loop inside each child; one "
+                   "child per pass")
+    elif sys.argv[1:2] == ["--lds-child"]:
+        child(LDS_SETTINGS, "lds=off")
+    elif sys.argv[1:2] == ["--lds-blocks-child"]:
+        child(LDS_SETTINGS, "lds=off", BLOCK_SHAPES)
+    elif sys.argv[1:2] == ["--lds-blocks"]:
+        spans_main("--lds-blocks-child", LDS_SETTINGS, "lds=off",
+                   "the --lds sweep over launches of 128 .. 1024 (bag, tile) blocks")
+    elif sys.argv[1:2] == ["--lds"]:
+        spans_main("--lds-child", LDS_SETTINGS, "lds=off",
+                   "tw_count_pairs_chain_planes under tw_count_chain_class_lds 1 (off), 2 (on) and "
+                   "the automatic rule (automatic class bits, swap, span and digit width): ms of "
+                   "the whole native call and the ratio of medians to off inside each child; one "
                    "child per pass")
     else:
         sys.exit(__doc__)

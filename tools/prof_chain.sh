@@ -14,7 +14,9 @@ timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/p1 -o r
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/p2 -o run -- $B > $O.p2.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INSTS_LDS --output-format csv -d $O/p3 -o run -- $B > $O.p3.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU --output-format csv -d $O/p4 -o run -- $B > $O.p4.log 2>&1
-python3 tools/pmc_summary.py $O/chain_count_pmc.json k_count_chain $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null
+# (the LDS-table form of the class count, DESIGN §4.1m: how busy the LDS is, and conflicts)
+timeout -s KILL 120 rocprofv3 --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT --output-format csv -d $O/p5 -o run -- $B > $O.p5.log 2>&1
+python3 tools/pmc_summary.py $O/chain_count_pmc.json k_count_chain $O/p1 $O/p2 $O/p3 $O/p4 $O/p5 > /dev/null
 python3 tools/pmc_summary.py $O/chain_emit_pmc.json k_chain_emit $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null
 # the count's pre-passes (the planes; with class bits the class-ordered z and the run tables)
 python3 tools/pmc_summary.py $O/chain_planes_pmc.json k_chain_planes $O/p1 $O/p2 $O/p3 $O/p4 > /dev/null

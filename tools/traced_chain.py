@@ -21,12 +21,14 @@ path, K, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
 # k_count_chain_planes<NB>, whose launch's time includes its pre-pass k_chain_planes<NB>, the
 # launch just before it on the stream, or its class-run form k_count_chain_classes<NB, K>, whose
 # time includes both pre-passes: k_chain_planes<NB> and k_chain_zclasses, or the one launch
-# that runs both, k_chain_prepass<NB>)
+# that runs both, k_chain_prepass<NB>; k_count_chain_classes_lds<NB, K> is the class-run form
+# with its low-field table in LDS)
 every = list(csv.DictReader(open(path)))
 rows = [r for r in every
         if ("k_count_chain<" in r["Kernel_Name"] and ", false>" in r["Kernel_Name"])
         or "k_count_chain_planes<" in r["Kernel_Name"]
-        or "k_count_chain_classes<" in r["Kernel_Name"]]
+        or "k_count_chain_classes<" in r["Kernel_Name"]
+        or "k_count_chain_classes_lds<" in r["Kernel_Name"]]
 pre = sorted((r for r in every if "k_chain_planes<" in r["Kernel_Name"]),
              key=lambda r: int(r["Start_Timestamp"]))
 pre2 = sorted((r for r in every if "k_chain_zclasses" in r["Kernel_Name"]),
@@ -50,7 +52,7 @@ def last_before(qs, r):
 
 
 def prepass_ms(r):
-    if "k_count_chain_classes<" in r["Kernel_Name"]:
+    if "k_count_chain_classes<" in r["Kernel_Name"] or "k_count_chain_classes_lds<" in r["Kernel_Name"]:
         f, z = last_row_before(fused, r), last_row_before(pre2, r)
         # (the form of THIS launch: whichever pre-pass ran last before it)
         if f is not None and (z is None or int(f["Start_Timestamp"]) > int(z["Start_Timestamp"])):

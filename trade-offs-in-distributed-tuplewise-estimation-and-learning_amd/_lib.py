@@ -258,6 +258,8 @@ _SIGNATURES = {
     "tw_count_chain_class_span": [_i32],
     "tw_count_chain_class_digits": [_i32],
     "tw_count_chain_class_digits_of": [_i32, _i32],
+    "tw_count_chain_class_lds": [_i32],
+    "tw_count_chain_class_lds_of": [_i32, _i32, _i64, _i64, _i64],
     "tw_count_chain_prepass": [_i32],
     "tw_count_chain_prepass_of": [_i32, _i32, _i64, _i64, _i64],
     "tw_triplet_rows_tile": [],

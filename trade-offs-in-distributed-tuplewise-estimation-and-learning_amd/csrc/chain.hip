@@ -732,7 +732,8 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_planes(
 // of any size goes through; the order inside a class is that of the cursors' atomics, which
 // the counts — integer sums — do not see.  With cp.digits > 0 (the digit loop)
 // an image is stored digit-ready (class_digit_encode; class_wide_encode where cp.dbits asks for
-// the wide digits of §4.1k): one word per image either way, written anew by every launch.
+// the wide digits of §4.1k, class_lds_encode for the LDS-table form of §4.1m): one word per image
+// in every form, written anew by every launch.
 __device__ __forceinline__ uint32_t class_block_scan(uint32_t v, uint32_t* wsum, int lane,
                                                      int wid) {
 #pragma unroll
@@ -751,33 +752,43 @@ __device__ __forceinline__ uint32_t class_block_scan(uint32_t v, uint32_t* wsum,
 // the word pre-pass 2 stores for a complemented z image under the launch's loop
 __device__ __forceinline__ uint32_t class_store_word(uint32_t zc, const ClassPlan& cp) {
   return cp.digits <= 0                 ? zc
+         : cp.dbits == kClassLdsBits  ? class_lds_encode(zc)
          : cp.dbits == kClassWideBits ? class_wide_encode(zc)
                                       : class_digit_encode(zc, cp.digits);
 }
 
-// The same word from the launch's form spelled out once per block: digit j is sh[j], mk[j]
+// The same word from the launch's form spelled out once per block: field j is bits sh[j] ..
+// of the image under mk[j], stored at bit at[j] (the digit loops: digit j in byte j; the
+// LDS-table form: the top digit at bit 0, the low byte at bit 9)
 struct ClassStoreForm {
   bool plain;  // the complemented image itself
-  int sh[kClassDigits];
+  int sh[kClassDigits], at[kClassDigits];
   uint32_t mk[kClassDigits];
 };
 __device__ __forceinline__ ClassStoreForm class_store_form(const ClassPlan& cp) {
   ClassStoreForm e{};
   e.plain = cp.digits <= 0;
-  const bool wide = cp.dbits == kClassWideBits;
+  const bool wide = cp.dbits == kClassWideBits, lds = cp.dbits == kClassLdsBits;
   const int nl = e.plain ? kClassDigitMaxNL : cp.digits;
 #pragma unroll
   for (int j = 0; j < kClassDigits; ++j) {
     e.sh[j] = wide ? kClassWideBits * j : class_digit_shift(nl, j);
     e.mk[j] = wide ? (j < kClassWideDigits ? (1u << kClassWideBits) - 1u : 0u)
                    : (1u << class_digit_width(nl, j)) - 1u;
+    e.at[j] = 8 * j;
+  }
+  if (lds) {  // class_lds_encode: two fields
+    e.sh[0] = kClassLdsBits, e.mk[0] = (1u << kClassWideBits) - 1u, e.at[0] = 0;
+    e.sh[1] = 0, e.mk[1] = (uint32_t)(kClassLdsEntries - 1), e.at[1] = 9;
+#pragma unroll
+    for (int j = 2; j < kClassDigits; ++j) e.sh[j] = 0, e.mk[j] = 0u, e.at[j] = 0;
   }
   return e;
 }
 __device__ __forceinline__ uint32_t class_store_word(uint32_t zc, const ClassStoreForm& e) {
   uint32_t w = 0;
 #pragma unroll
-  for (int j = 0; j < kClassDigits; ++j) w |= ((zc >> e.sh[j]) & e.mk[j]) << (8 * j);
+  for (int j = 0; j < kClassDigits; ++j) w |= ((zc >> e.sh[j]) & e.mk[j]) << e.at[j];
   return e.plain ? zc : w;
 }
 
@@ -1023,6 +1034,61 @@ __global__ __launch_bounds__(kBlock) void k_count_chain_classes(
   count_chain_epilogue(tot, active, v, wid, lane, out);
 }
 
+// The count on class runs with the low field's carries tabulated in LDS (chainclass.h's
+// class_lds_*): one block of kClassLdsThreads threads — 16 waves, one block per
+// CU at 4 waves per SIMD — per (bag, x tile of two groups), grid = bags x p.tiles_x in
+// xcd_block order.  The block tabulates the tile's 256 low-field carries per lane and group
+// (128 KiB), then its waves draw the bag's runs from an LDS counter and count them with
+// bits_count_runs_lds: 5 VALU per z instead of the wide loop's 8.  All waves belong to one bag:
+// a block sum and one u64 atomic (the pre-pass zeroed the counts).  Exists for NB - K = 12;
+// the launcher plans it with p.R = 2, no swapped items and images written by class_lds_encode
+// (cp.dbits = kClassLdsBits).
+constexpr int kClassLdsThreads = 1024;
+constexpr int kClassLdsWaves = kClassLdsThreads / kWave;
+static_assert(kClassLdsWaves * 16 == kClassLdsEntries, "wave w writes the 16 entries d1 = w");
+static_assert(kClassLdsTableBytes + kClassLdsWaves * 8 + 8 <= 160 * 1024, "the CU's LDS");
+template <int NB, int K>
+__global__ __launch_bounds__(kClassLdsThreads) void k_count_chain_classes_lds(
+    const int64_t* __restrict__ x_off, const int64_t* __restrict__ z_off, int n_shards,
+    int n_bags, PlanesPlan p, ClassPlan cp, const uint32_t* __restrict__ work,
+    unsigned long long* __restrict__ out) {
+  __shared__ uint2 table[kClassLdsEntries * kWave];
+  __shared__ unsigned long long part[kClassLdsWaves];
+  __shared__ uint32_t next;
+  static_assert(sizeof(table) == kClassLdsTableBytes, "chainclass.h's layout");
+  const int lb = xcd_block(blockIdx.x, gridDim.x);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int v = lb / p.tiles_x, tx = lb - v * p.tiles_x;  // v < n_bags: the grid is exact
+  const int s = v % n_shards;
+  const int64_t nx = x_off[s + 1] - x_off[s], nz = z_off[s + 1] - z_off[s];
+  const PlanesBag bag = planes_bag(nx, nz, p.swap != 0);
+  const int lim = bag.xgroups < p.gx ? bag.xgroups : p.gx;
+  const int g0 = tx * p.R;
+  const int ng = __builtin_amdgcn_readfirstlane(lim - g0 < p.R ? lim - g0 : p.R);
+  // (the bag's count is <= cp.cap: no entry past the bag's table is read)
+  const int cnt = __builtin_amdgcn_readfirstlane((int)work[cp.off_cnt + v]);
+  if (v >= n_bags || ng <= 0 || cnt <= 0) return;  // block-uniform, before the barriers
+  const uint32_t* __restrict__ tab = work + bits_uniform(cp.off_tab + (int64_t)v * cp.cap * 2);
+  const uint32_t* __restrict__ pw =
+      work + bits_uniform(planes_word(NB, (int64_t)v * p.gx + g0, 0, 0));
+  const uint32_t* __restrict__ zbag = work + bits_uniform(cp.off_zs + (int64_t)v * cp.zs_stride);
+  if (threadIdx.x == 0) next = 0;
+  class_lds_build<NB>(table, pw, wid, lane, ng);
+  __syncthreads();
+  const uint32_t lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint2*)table;
+  const unsigned long long t =
+      wave_sum_u64(bits_count_runs_lds<NB, K>(lds, pw, zbag, tab, cnt, &next, lane, ng));
+  if (lane == 0) part[wid] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int w = 0; w < kClassLdsWaves; ++w) sum += part[w];
+    if (sum) atomicAdd(out + v, sum);
+  }
+}
+
 // The swapped items of a plan whose plane items went through class runs: per bag
 // p.tiles_s x p.schunks items, the x remainder as scalars against the bag's z planes, the
 // full-NB loop and the decode of k_count_chain_planes unchanged.  Adds to the same counts.
@@ -1209,6 +1275,7 @@ static int g_planes_swap = 1;  // (tw_count_chain_set_swap: 0 never, 1 automatic
 static int g_class_bits = -1;  // (tw_count_chain_set_class_bits: -1 automatic, 0 off, 1..8)
 static int g_class_span = 0;   // (tw_count_chain_class_span: 0 automatic, >= 1 entries per item)
 static int g_class_digits = 0;  // (tw_count_chain_class_digits: 0 automatic, 3 or 4 planes)
+static int g_class_lds = 0;     // (tw_count_chain_class_lds: 0 automatic, 1 off, 2 on)
 static int g_prepass = 0;  // (tw_count_chain_prepass: 0 automatic, 1 separate launches, 2 fused)
 // class bits of a bit-sliced launch: forced (clamped to its planes), or chainclass.h's
 // automatic rule
@@ -1798,6 +1865,13 @@ static void count_chain_launch_planes(const PlanesPlan& p, const ClassPlan& cp, 
 #define TW_CLASS_CASE(K)                                                                       \
   case K:                                                                                      \
     if constexpr (class_wide_fit(NB - K)) {                                                    \
+      if (cp.dbits == kClassLdsBits) { /* one block per (bag, x tile): DESIGN §4.1m */         \
+        hipLaunchKernelGGL((k_count_chain_classes_lds<NB, K>),                                 \
+                           dim3((unsigned)((int64_t)bags * p.tiles_x)), dim3(kClassLdsThreads), \
+                           0, st, d_x_off, d_z_off, n_shards, bags, p, cp,                     \
+                           (const uint32_t*)work, o);                                          \
+        break;                                                                                 \
+      }                                                                                        \
       if (cp.dbits == kClassWideBits) {                                                        \
         hipLaunchKernelGGL((k_count_chain_classes<NB, K, kClassWideBits>), g, b, 0, st,        \
                            d_x_off, d_z_off, n_shards, bags, p, cp, (const uint32_t*)work, o); \
@@ -1830,6 +1904,19 @@ static int64_t chain_planes_work_bytes(int64_t bags, int64_t max_nx, int64_t max
          (int64_t)sizeof(uint32_t);
 }
 
+// The plan of a launch that runs a digit loop (form 3) of dbits planes per digit.  The digit
+// loops' register maps hold kClassDigitsMaxR groups: the plan's tiles follow.  (A padded slot's
+// price in the swap rule is that of the loop the launch runs; the LDS-table form plans as the
+// wide loop it replaces.)
+static PlanesPlan chain_digits_plan(int64_t max_nx, int64_t max_nz, int64_t bags, int nb, int k,
+                                    int dbits) {
+  int R = g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0;
+  R = R == 0 || R > kClassDigitsMaxR ? kClassDigitsMaxR : R;
+  const int ndigits = dbits == kClassWideBits ? kClassWideDigits : kClassDigits;
+  return planes_plan(max_nx, max_nz, bags, R, g_chain_zchunk,
+                     class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k, ndigits + 1));
+}
+
 // The count launch of the _planes entries on an output already zeroed (zero_out: zeroed here,
 // by a launch of its own or inside the fused pre-pass): where chainplan.h's
 // chain_count_sliced says so, the pre-pass and k_count_chain_planes (tuning hook: R = largest
@@ -1857,16 +1944,13 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
   // (under class runs the automatic swap also asks which remainder costs fewer instructions)
   // The digit loop's register map holds kClassDigitsMaxR groups: the plan's tiles follow
   const bool digits = k > 0 && class_loop_form(nb, k) == 3;
-  int R = g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0;
-  if (digits) R = R == 0 || R > kClassDigitsMaxR ? kClassDigitsMaxR : R;
   // planes per digit: the wide split where it fits and the hook's setting asks for it
   const int dbits = digits ? class_digit_bits(nb, k, g_class_digits) : kClassDigitBits;
-  const int ndigits = dbits == kClassWideBits ? kClassWideDigits : kClassDigits;
-  // (a padded slot's price in the swap rule is that of the loop this launch runs)
   const PlanesPlan p =
-      planes_plan(max_nx, max_nz, bags, R, g_chain_zchunk,
-                  class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k,
-                                  digits ? ndigits + 1 : 0));
+      digits ? chain_digits_plan(max_nx, max_nz, bags, nb, k, dbits)
+             : planes_plan(max_nx, max_nz, bags, g_chain_R >= 1 && g_chain_R <= 4 ? g_chain_R : 0,
+                           g_chain_zchunk,
+                           class_swap_mode(g_planes_swap, max_nx, max_nz, nb, k, 0));
   // entries per item: the digit loop walks a span (forced, or chainclass.h's automatic rule);
   // the masked-plane loop's registers are class-dependent throughout: one run per item
   int64_t runs = 1;
@@ -1876,7 +1960,8 @@ static int count_chain_launch_work(const void* d_x_bag, const int64_t* d_x_off, 
                : class_span_auto(bags, p.tiles_x, (int)class_capacity(max_nz, k, p.z_chunk));
   ClassPlan cp = class_plan(p, max_nx, max_nz, bags, nb, k, runs);
   cp.digits = digits ? nb - k : 0;
-  cp.dbits = digits ? dbits : 0;
+  // the LDS-table form where the launch would run the wide loop and the setting asks for it
+  cp.dbits = !digits ? 0 : class_lds_runs(g_class_lds, dbits, p, bags) ? kClassLdsBits : dbits;
   TW_ARG_CHECK(bags * (int64_t)p.per_bag < (1ll << 31) &&
                    bags * (int64_t)(p.gx + p.gz) < (1ll << 31) &&
                    (!fused || prepass_grid_fits(bags, p.gx, p.gz)) &&
@@ -1932,6 +2017,35 @@ extern "C" int32_t tw_count_chain_class_digits(int32_t w) {
                "tw_count_chain_class_digits: 0 (automatic), 3, 4 or -1 (report)");
   g_class_digits = w;
   return before;
+}
+
+// The LDS-table form of the class count (chainclass.h): 0 the automatic rule, 1
+// off — every launch is the digit loops' —, 2 on wherever the form fits (the launch would run
+// the wide digits, two groups per tile, no swapped items), -1 only reports.  Returns the setting
+// in force before the call; anything else changes nothing and returns TW_ERR_ARG.
+// tw_count_chain_class_span has no effect on launches of this form.
+extern "C" int32_t tw_count_chain_class_lds(int32_t mode) {
+  const int32_t before = g_class_lds;
+  if (mode == -1) return before;
+  TW_ARG_CHECK(mode >= 0 && mode <= 2,
+               "tw_count_chain_class_lds: 0 (automatic), 1 (off), 2 (on) or -1 (report)");
+  g_class_lds = mode;
+  return before;
+}
+
+// 1 if a strict launch of tw_count_pairs_chain_planes with these arguments runs the LDS-table
+// form under the current settings, 0 otherwise
+extern "C" int32_t tw_count_chain_class_lds_of(int32_t n_shards, int32_t steps, int64_t max_nx,
+                                               int64_t max_nz, int64_t image_bound) {
+  if (n_shards <= 0 || steps <= 0 || max_nx <= 0 || max_nz <= 0) return 0;
+  const int64_t bags = (int64_t)n_shards * steps;
+  const int nb = bits_pick_nb(image_bound);
+  if (!chain_count_sliced(max_nx, g_chain_R, false, nb)) return 0;
+  const int k = chain_class_bits(max_nz, bags, nb);
+  if (k <= 0 || class_loop_form(nb, k) != 3) return 0;
+  const int dbits = class_digit_bits(nb, k, g_class_digits);
+  const PlanesPlan p = chain_digits_plan(max_nx, max_nz, bags, nb, k, dbits);
+  return class_lds_runs(g_class_lds, dbits, p, bags) ? 1 : 0;
 }
 
 // The planes per digit a launch of (nb, k) runs under the current setting: 4 where it runs the

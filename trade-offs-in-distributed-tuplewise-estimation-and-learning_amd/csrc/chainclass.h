@@ -272,6 +272,82 @@ TW_BITS_HD int class_digit_bits(int nb, int k, int setting) {
   return want == kClassWideBits && class_wide_fit(nb - k) ? kClassWideBits : kClassDigitBits;
 }
 
+// ------------------------------------------------------------- the low-field table in LDS
+// A third form of the 12-plane low field.  The wide loop's carry after its first
+// two steps — digits 0 and 1, the low 8 planes — does not depend on the class: it is one of 256
+// words per lane, fixed for an x tile.  A block tabulates them once in LDS and its waves read
+// the word of a z image's low byte d8 from there; per z and group only the top digit's step
+// under E and the popcount are left.
+//  Layout: entry d8, lane l is the 8 bytes {group 0 word, group 1 word} at byte
+// d8 * kClassLdsEntryBytes + l * 8; 256 entries of two groups end at kClassLdsTableBytes.
+constexpr int kClassLdsBits = 8;      // ClassPlan::dbits of this form: planes the table covers
+constexpr int kClassLdsGroups = 2;    // x groups of a tile (one 8-byte read serves both)
+constexpr int kClassLdsEntries = 1 << kClassLdsBits;
+constexpr int kClassLdsEntryBytes = 64 * 4 * kClassLdsGroups;
+constexpr int kClassLdsTableBytes = kClassLdsEntries * kClassLdsEntryBytes;
+constexpr uint32_t kClassLdsOffsetMask = (uint32_t)(kClassLdsEntries - 1) * kClassLdsEntryBytes;
+static_assert(kClassLdsEntryBytes == 512 && kClassLdsTableBytes == 131072 &&
+                  kClassLdsOffsetMask == 0x1FE00u,
+              "the constants named in the loop's statements");
+// The digit-ready word of this form: the top digit (planes 8 .. 11) in bits [3:0] — the byte the
+// VGPR index mode reads, below 16 — and the low byte d8 in bits [16:9], so that
+// word & kClassLdsOffsetMask is the byte offset of entry d8.  Every other bit is zero.
+TW_BITS_HD uint32_t class_lds_encode(uint32_t zc) {
+  return ((zc >> kClassLdsBits) & ((1u << kClassWideBits) - 1u)) |
+         ((zc & (uint32_t)(kClassLdsEntries - 1)) << 9);
+}
+TW_BITS_HD uint32_t class_lds_top(uint32_t word) { return word & ((1u << kClassWideBits) - 1u); }
+TW_BITS_HD uint32_t class_lds_offset(uint32_t word) { return word & kClassLdsOffsetMask; }
+// the complemented image's low 12 bits again
+TW_BITS_HD uint32_t class_lds_decode(uint32_t word) {
+  return (class_lds_top(word) << kClassLdsBits) | (class_lds_offset(word) / kClassLdsEntryBytes);
+}
+// Entry d8 of a group: t's digit tables 0 and 1 (class_wide_tables_one<0>, <1> under ~0u)
+TW_BITS_HD uint32_t class_lds_entry(const ClassWideTables& t, uint32_t d8) {
+  const uint32_t d0 = d8 & 15u, d1 = (d8 >> 4) & 15u;
+  return bits_carry(t.g[1][d1], t.g[1][d1 + 1], t.g[0][d0]);
+}
+// class_gt32_masked through the table: c_low = class_lds_entry of the word's low byte, top the
+// top digit's table under E (t.g[2] of class_wide_tables)
+TW_BITS_HD ClassMasked class_gt32_lds(uint32_t c_low, const uint32_t (&top)[kClassWideEntries],
+                                      uint32_t G, uint32_t word) {
+  const uint32_t d = class_lds_top(word);
+  return ClassMasked{G, bits_carry(top[d], top[d + 1], c_low)};
+}
+// Words the loop's scalar loads may read past a run's end (never used): they stay inside the
+// count region behind the class-ordered images, as the other loops' batches do
+constexpr int kClassLdsOverReadWords = 8;
+static_assert(kClassLdsOverReadWords < 64, "the over-read must stay inside the count region");
+// The form takes the launches the wide loop takes
+constexpr bool class_lds_fit(int nl) { return class_wide_fit(nl); }
+// Whether a launch runs the form.  mode: tw_count_chain_class_lds' setting (0 automatic, 1 off,
+// 2 on wherever it fits); dbits: the planes per digit the launch's digit loop would run; p: its
+// plan.  It fits where that loop is the wide one, a tile is kClassLdsGroups groups and the plan
+// has no swapped items.
+//  The automatic rule.  The launch is one block per (bag, x tile) and a block fills a CU, so the
+// chip takes the blocks in rounds of kClassLdsCus while the wide loop's wave items fill it
+// evenly: the form gains 0.72 - 0.76 of the wide launch's time at whole rounds and loses where
+// a short last round leaves most CUs idle.  Sweep over 128 .. 1024 blocks (DESIGN §4.1m,
+// profiles/r17_classlds_blocks_ab.json; ratio to the wide loop): 128 blocks 1.09 - 1.10, 192
+// 0.87, 256 0.72, 320 1.03 - 1.04, 384 0.90, 448 0.82, 512 0.74, 576 0.93, 640 0.86, 768 0.75, 832
+// 0.89, 1024 0.75.  So: from kClassLdsMinBlocks on; in the second round only from half a round;
+// in the third from a quarter (576 is measured, 513 .. 575 are not); any later round.
+constexpr int64_t kClassLdsCus = 256, kClassLdsMinBlocks = 192;
+TW_BITS_HD bool class_lds_auto(int64_t blocks) {
+  if (blocks < kClassLdsMinBlocks) return false;
+  const int64_t rounds = planes_ceil_div(blocks, kClassLdsCus);
+  const int64_t last = blocks - (rounds - 1) * kClassLdsCus;  // blocks of the last round
+  if (rounds == 2) return 2 * last >= kClassLdsCus;
+  if (rounds == 3) return 4 * last >= kClassLdsCus;
+  return true;
+}
+TW_BITS_HD bool class_lds_runs(int mode, int dbits, const PlanesPlan& p, int64_t n_bags) {
+  if (mode == 1 || dbits != kClassWideBits || p.R != kClassLdsGroups ||
+      p.tiles_s * p.schunks != 0)
+    return false;
+  return mode == 2 || class_lds_auto(n_bags * p.tiles_x);
+}
+
 // ---------------------------------------------------------------------------- the run table
 // Per bag: for each non-empty class, ceil(n_c / chunk) runs of near-equal length over the
 // class's range of the class-ordered region, classes in ascending order.  An entry is two u32
@@ -1045,6 +1121,187 @@ __device__ __forceinline__ unsigned long long bits_count_span_wide_of(
   if constexpr (R > 1)
     if (ng < R) return bits_count_span_wide_of<NB, K, R - 1>(pw, zbag, tab, n, lane, ng);
   return bits_count_span_wide<NB, K, R>(pw, zbag, tab, n, lane);
+}
+
+// The LDS-table loop: the wide loop with its first two steps read from the
+// block's table (class_lds_*).  Per z: s_and (the entry's offset), one v_add_u32 (offset + the
+// lane's table address), one ds_read_b64 (both groups' words), one s_set_gpr_idx_idx; per z and
+// group one v_bitop3 on the top digit's table — its third source the word read — and one v_bcnt:
+// 5 VALU + 2 SALU + 1 LDS per z at two groups (the trip's own 9 scalar instructions per 8 z on
+// top).  A whole run is ONE asm statement, so nothing the compiler allocates lives in the
+// registers named here while LDS reads are in flight.  Register map, all of it clobbers or
+// pinned inputs: two sets of carries, A = v8 .. v15 and B = v16 .. v23 (image u, group g:
+// v(base + 2u + g), the pair one ds_read_b64 fills); v4, v5 the LDS addresses; the top digit's
+// 17 entries of group 0 in v24 .. v40, of group 1 in v42 .. v58 (tuples start even); the eight
+// words at hand in s40 .. s47 (W), the eight after them in s48 .. s55 (N), s56 a temporary.
+//  A trip of the main loop takes two batches of four images: it loads N, reads batch 1's words
+// from LDS into B while the chains of batch 0 run on A, then reads the next trip's batch 0 into
+// A (from N) while the chains of batch 1 run on B.  Every wait is s_waitcnt lgkmcnt(0): scalar
+// loads return out of order and share the counter with LDS.  The LDS instructions and the
+// address adds sit outside s_set_gpr_idx_on / _off.  Only words of the run reach M0 or an LDS
+// address: a set is read ahead for a WHOLE batch only (the main loop runs while 12 images are
+// left), the last 1 .. 3 images go one at a time.  The scalar loads read up to 8 words past the
+// run's end — inside the workspace, as in bits_count_class — and never use them.
+constexpr int kClassLdsTopBase0 = 24, kClassLdsTopBase1 = 42;
+static_assert(kClassLdsTopBase0 + kClassWideEntries - 1 == 40 && kClassLdsTopBase1 % 2 == 0 &&
+                  kClassLdsTopBase1 > 40 && kClassLdsTopBase1 + kClassWideEntries - 1 == 58,
+              "the registers named below");
+static_assert(kClassLdsOverReadWords == 8, "the loop's eight-word loads");
+#define TW_LD_RD(Z, A, C) \
+  "s_and_b32 s56, " Z ", 0x1fe00\n\tv_add_u32 " A ", s56, %[l8]\n\tds_read_b64 " C ", " A "\n\t"
+#define TW_LD_OPS(C0, C1) TW_DG_OP(C0, "v24", "v25") TW_DG_OP(C1, "v42", "v43")
+#define TW_LD_CNT(C0, C1) TW_DG_CNT(C0, "%[n0]") TW_DG_CNT(C1, "%[n1]")
+// the LDS reads of four images' words into a set (its pairs P0 .. P3)
+#define TW_LD_READS(Z0, Z1, Z2, Z3, P0, P1, P2, P3) \
+  TW_LD_RD(Z0, "v4", P0) TW_LD_RD(Z1, "v5", P1) TW_LD_RD(Z2, "v4", P2) TW_LD_RD(Z3, "v5", P3)
+// the chains and popcounts of the four images whose words a set holds
+#define TW_LD_CHAINS(Z0, Z1, Z2, Z3, C0, C1, C2, C3, C4, C5, C6, C7)          \
+  "s_set_gpr_idx_on " Z0 ", 0x3\n\t" TW_LD_OPS(C0, C1)                        \
+  "s_set_gpr_idx_idx " Z1 "\n\t" TW_LD_OPS(C2, C3)                            \
+  "s_set_gpr_idx_idx " Z2 "\n\t" TW_LD_OPS(C4, C5)                            \
+  "s_set_gpr_idx_idx " Z3 "\n\t" TW_LD_OPS(C6, C7) "s_set_gpr_idx_off\n\t"    \
+  TW_LD_CNT(C0, C1) TW_LD_CNT(C2, C3) TW_LD_CNT(C4, C5) TW_LD_CNT(C6, C7)
+#define TW_LD_ONE(Z)                                                          \
+  TW_LD_RD(Z, "v4", "v[8:9]") "s_waitcnt lgkmcnt(0)\n\ts_set_gpr_idx_on " Z ", 0x3\n\t" \
+  TW_LD_OPS("v8", "v9") "s_set_gpr_idx_off\n\t" TW_LD_CNT("v8", "v9")
+#define TW_LD_W0 "s40", "s41", "s42", "s43"
+#define TW_LD_W1 "s44", "s45", "s46", "s47"
+#define TW_LD_N0 "s48", "s49", "s50", "s51"
+#define TW_LD_SET_A "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15"
+#define TW_LD_SET_B "v16", "v17", "v18", "v19", "v20", "v21", "v22", "v23"
+#define TW_LD_PAIRS_A "v[8:9]", "v[10:11]", "v[12:13]", "v[14:15]"
+#define TW_LD_PAIRS_B "v[16:17]", "v[18:19]", "v[20:21]", "v[22:23]"
+#define TW_LD_X(M, ...) M(__VA_ARGS__)
+#define TW_LD_W_FROM_N                                                        \
+  "s_mov_b64 s[40:41], s[48:49]\n\ts_mov_b64 s[42:43], s[50:51]\n\t"          \
+  "s_mov_b64 s[44:45], s[52:53]\n\ts_mov_b64 s[46:47], s[54:55]\n\t"
+// rem: the images left (>= 1 on entry, 0 on exit); off: the byte offset of W's words from p
+#define TW_LD_RUN                                                                          \
+  "s_load_dwordx8 s[40:47], %[p], 0x0\n\ts_waitcnt lgkmcnt(0)\n\t"                         \
+  "s_cmp_lt_u32 %[rem], 4\n\ts_cbranch_scc1 3f\n\t"                                        \
+  TW_LD_X(TW_LD_READS, TW_LD_W0, TW_LD_PAIRS_A) "s_waitcnt lgkmcnt(0)\n\t"                 \
+  "s_cmp_lt_u32 %[rem], 12\n\ts_cbranch_scc1 1f\n\t"                                       \
+  "0:\n\t" /* >= 12 left: batches 0 and 1 and the next trip's batch 0 are whole */         \
+  "s_load_dwordx8 s[48:55], %[p], %[off] offset:0x20\n\t"                                  \
+  TW_LD_X(TW_LD_READS, TW_LD_W1, TW_LD_PAIRS_B) TW_LD_X(TW_LD_CHAINS, TW_LD_W0, TW_LD_SET_A) \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                               \
+  TW_LD_X(TW_LD_READS, TW_LD_N0, TW_LD_PAIRS_A) TW_LD_X(TW_LD_CHAINS, TW_LD_W1, TW_LD_SET_B) \
+  "s_waitcnt lgkmcnt(0)\n\t" TW_LD_W_FROM_N                                                \
+  "s_add_u32 %[off], %[off], 32\n\ts_sub_u32 %[rem], %[rem], 8\n\t"                        \
+  "s_cmp_ge_u32 %[rem], 12\n\ts_cbranch_scc1 0b\n\t"                                       \
+  "1:\n\t" /* 4 .. 11 left, set A holds the words of W's batch 0 */                        \
+  "s_cmp_lt_u32 %[rem], 8\n\ts_cbranch_scc1 2f\n\t"                                        \
+  "s_load_dwordx8 s[48:55], %[p], %[off] offset:0x20\n\t"                                  \
+  TW_LD_X(TW_LD_READS, TW_LD_W1, TW_LD_PAIRS_B) TW_LD_X(TW_LD_CHAINS, TW_LD_W0, TW_LD_SET_A) \
+  "s_waitcnt lgkmcnt(0)\n\t" TW_LD_X(TW_LD_CHAINS, TW_LD_W1, TW_LD_SET_B) TW_LD_W_FROM_N   \
+  "s_sub_u32 %[rem], %[rem], 8\n\ts_branch 3f\n\t"                                         \
+  "2:\n\t" /* 4 .. 7 left */                                                               \
+  TW_LD_X(TW_LD_CHAINS, TW_LD_W0, TW_LD_SET_A)                                             \
+  "s_mov_b64 s[40:41], s[44:45]\n\ts_mov_b64 s[42:43], s[46:47]\n\t"                       \
+  "s_sub_u32 %[rem], %[rem], 4\n\t"                                                        \
+  "3:\n\t" /* 0 .. 3 left, their words in s40, s41, s42 */                                 \
+  "s_cmp_eq_u32 %[rem], 0\n\ts_cbranch_scc1 4f\n\t" TW_LD_ONE("s40")                       \
+  "s_cmp_eq_u32 %[rem], 1\n\ts_cbranch_scc1 4f\n\t" TW_LD_ONE("s41")                       \
+  "s_cmp_eq_u32 %[rem], 2\n\ts_cbranch_scc1 4f\n\t" TW_LD_ONE("s42")                       \
+  "4:\n\ts_mov_b32 %[rem], 0"
+#define TW_LD_TAB(t16, t1)                                                    \
+  "{v[24:39]}"(t16[0]), "{v40}"(t1[0]), "{v[42:57]}"(t16[1]), "{v58}"(t1[1])
+#define TW_LD_CLOBBERS                                                                         \
+  "scc", "v4", "v5", TW_LD_SET_A, TW_LD_SET_B, TW_LD_W0, TW_LD_W1, TW_LD_N0, "s52", "s53",     \
+      "s54", "s55", "s56"
+
+// One block's count of one (bag, x tile of two groups) on the LDS table.  lds: the byte address
+// of the block's table of kClassLdsTableBytes (built by class_lds_build below, behind a
+// barrier); pw: the tile's planes; zbag: the bag's class-ordered images (class_lds_encode);
+// tab, cnt: the bag's run table and its entry count; next: an LDS counter, zero at the barrier,
+// from which the block's waves draw runs — or null: wave wid of waves takes entries wid,
+// wid + waves, ... (the striped assignment measured against the counter in DESIGN §4.1m).  ng:
+// the tile's groups (1 or 2; a missing group's planes read as zero).  Returns the lane's count
+// over the runs its wave took.
+template <int NB, int K>
+__device__ __forceinline__ unsigned long long bits_count_runs_lds(
+    uint32_t lds, const uint32_t* __restrict__ pw, const uint32_t* __restrict__ zbag,
+    const uint32_t* __restrict__ tab, int cnt, uint32_t* next, int lane, int ng, int wid = 0,
+    int waves = 1) {
+  constexpr int NL = NB - K, W = kClassWideBits, S = W * (kClassWideDigits - 1);
+  static_assert(class_lds_fit(NL), "the table covers the low 8 planes of a 12-plane low field");
+  typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+  const ConstWords ct = (ConstWords)(uintptr_t)tab;
+  [[maybe_unused]] const ConstWords zc = (ConstWords)(uintptr_t)zbag;
+  [[maybe_unused]] const uint32_t l8 = lds + 8u * (uint32_t)lane;
+  ClassVec16 t16[kClassLdsGroups];
+  uint32_t t1[kClassLdsGroups], acc[kClassLdsGroups] = {0u, 0u};
+  uint32_t cg = 0;  // sum of len * popc(G) over the wave's runs
+  for (int e = wid;; e += waves) {
+    if (next != nullptr) {
+      if (lane == 0) e = (int)atomicAdd(next, 1u);
+      e = __builtin_amdgcn_readfirstlane(e);
+    }
+    if (e >= cnt) break;
+    const ClassRun run = class_entry(ct[2 * e], ct[2 * e + 1]);
+    // the class's G, P and E and the top digit's table under E (bits_count_span_wide's rebuild;
+    // consecutive entries go to different waves: every run rebuilds)
+    uint32_t ngp = 0;
+    int ql = lane;  // (opaque per run: the reloads are not hoisted out of the loop)
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(ql));
+#endif
+#pragma unroll
+    for (int r = 0; r < kClassLdsGroups; ++r) {
+      uint32_t G, P, g[kClassWideEntries], tp[K], hp[W];
+      const bool has = r < ng;  // wave-uniform
+#pragma unroll
+      for (int b = 0; b < K; ++b) tp[b] = has ? pw[(r * NB + NL + b) * 64 + ql] : 0u;
+#pragma unroll
+      for (int b = 0; b < W; ++b) hp[b] = has ? pw[(r * NB + S + b) * 64 + ql] : 0u;
+      class_gp<K>(tp, run.cls, G, P);
+      ngp = bits_popc_add(G, ngp);
+      class_digit_table<W>(hp, class_equal_mask(G, P), g);
+#pragma unroll
+      for (int d = 0; d < (1 << W); ++d) t16[r][d] = g[d];
+      t1[r] = g[1 << W];
+    }
+    cg += (uint32_t)run.len * ngp;  // the run's exact length
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t rem = (uint32_t)run.len, off = 0;  // >= 1: only non-empty classes have runs
+    asm volatile(TW_LD_RUN
+                 : [n0] "+v"(acc[0]), [n1] "+v"(acc[1]), [rem] "+s"(rem), [off] "+s"(off)
+                 : [p] "s"(zc + run.z0), [l8] "v"(l8), TW_LD_TAB(t16, t1)
+                 : TW_LD_CLOBBERS);
+#endif
+  }
+  return (unsigned long long)cg + acc[0] + acc[1];
+}
+
+// The block's table: every wave builds digit tables 0 and 1 of both groups from the low 8
+// planes; wave w (of 16) writes the 16 entries with d1 = w, one 8-byte store per entry and lane.
+// The caller's barrier follows.  tab2: the table as {group 0, group 1} pairs, [entry][lane].
+template <int NB>
+__device__ __forceinline__ void class_lds_build(uint2* tab2, const uint32_t* __restrict__ pw,
+                                                int wid, int lane, int ng) {
+  ClassWideTables t[kClassLdsGroups];
+#pragma unroll
+  for (int r = 0; r < kClassLdsGroups; ++r) {
+    uint32_t low[kClassWideNL];
+#pragma unroll
+    for (int b = 0; b < kClassLdsBits; ++b) low[b] = r < ng ? pw[(r * NB + b) * 64 + lane] : 0u;
+#pragma unroll
+    for (int b = kClassLdsBits; b < kClassWideNL; ++b) low[b] = 0u;
+    class_wide_tables_one<0>(low, ~0u, t[r]);
+    class_wide_tables_one<1>(low, ~0u, t[r]);
+  }
+  uint32_t a[kClassLdsGroups] = {0u, 0u}, b[kClassLdsGroups] = {0u, 0u};  // T1[w], T1[w + 1]
+#pragma unroll
+  for (int d = 0; d < kClassWideEntries; ++d)
+#pragma unroll
+    for (int r = 0; r < kClassLdsGroups; ++r) {
+      a[r] = wid == d ? t[r].g[1][d] : a[r];
+      b[r] = wid + 1 == d ? t[r].g[1][d] : b[r];
+    }
+#pragma unroll
+  for (int d0 = 0; d0 < 16; ++d0)
+    tab2[(wid * 16 + d0) * 64 + lane] =
+        make_uint2(bits_carry(a[0], b[0], t[0].g[0][d0]), bits_carry(a[1], b[1], t[1].g[0][d0]));
 }
 #endif  // __HIPCC__
 
