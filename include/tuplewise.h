@@ -1245,6 +1245,54 @@ int tw_self_sorted(const void* d_s, const int64_t* d_off, int32_t n_shards, int6
                    int64_t max_n, int32_t dtype, int32_t kern, int32_t chunk, void* d_work,
                    void* d_out, void* stream);
 
+/* ---- Kendall tau matrices over many columns (csrc/kendall.hip; tuplewise.kendall; DESIGN.md
+ * §4.18; an extension, not in the reference).  With s_a(i, j) = sign(S[i, a] - S[j, a]) over the
+ * rows of one shard,
+ *     M[a, b] = sum_{i<j} s_a(i, j) s_b(i, j)      C - D of columns a and b (exact int64)
+ *     U_a     = M[a, a]                            the pairs not tied in column a
+ * so tau-a = M[a, b] / P and tau-b = M[a, b] / (sqrt(U_a) sqrt(U_b)).  Two steps:
+ *
+ * tw_col_ranks: d_s is row-major (rows, p) of TW_F64 or TW_I64, d_off[n_shards + 1] counts rows
+ * as in tw_self_pairs (shards of any mix of sizes in one call).  Every column of every shard is
+ * replaced by its strict-less ranks r_i = #{j in the shard : x_j < x_i}: equal values get equal
+ * ranks and sign(r_i - r_j) = sign(x_i - x_j) (-0.0 ties with 0.0, +-inf are ordinary values,
+ * TW_I64 is compared as int64; the input must hold no NaN).  The rank image d_ranks is
+ * column-major per shard with no padding: shard s starts at element (d_off[s] - d_off[0]) p,
+ * column c of it n_s elements after c n_s, total_n p elements in all.  width 16: uint16
+ * elements holding r - 32768 as an int16 bit pattern (shards of at most 65536 rows); width 32:
+ * int32.  tw_kendall_matrix_width(max_n) is the width tuplewise.kendall uses: 32 above 65536 rows,
+ * else the hook's value, else 16.  The sorts work on chunks of tw_col_ranks_chunk(max_n) <= 16384
+ * keys; d_work holds tw_col_ranks_work_bytes(...) bytes and needs no zeroing.
+ *
+ * tw_kendall_matrix: two rank images of the SAME shards (d_off, width), columns A (pa) and B
+ * (pb), each 1..1024; the same pointer and pa == pb is the symmetric call.  Per shard d_m holds
+ * pa x pb int64 (row-major), d_ua pa and d_ub pb int64; a shard of fewer than 2 rows gives zeros.
+ * Columns run in groups of 64, all group pairs in one launch; the symmetric call computes the
+ * group pairs ga <= gb and the upper 16 x 16 blocks only and mirrors them, so M == M^T exactly
+ * and Ua == Ub == diag(M).  Work items are the tile pairs of the triangle of
+ * tw_kendall_matrix_tile() rows per tile edge, each unordered pair of rows once.  The integers
+ * do not depend on scheduling (integer atomics); the caller zeroes nothing; d_work holds
+ * tw_kendall_matrix_work_bytes(...) bytes.  Hooks (0 restores the default): _set_width(0 | 16 |
+ * 32), _set_flush(k): the int32 accumulators are added to the int64 sums every k matrix
+ * instructions as well as after every tile pair, _set_plan(max_wgs): at most max_wgs workgroups
+ * per shard and group pair; each returns a status like every other entry, and all three are swept
+ * at small shapes by tests/test_gpu_kendall_matrix.py.  Argument errors return TW_ERR_ARG before
+ * any device work. */
+int32_t tw_kendall_matrix_tile(void);
+int32_t tw_kendall_matrix_width(int64_t max_n);
+int32_t tw_col_ranks_chunk(int64_t max_n);
+int32_t tw_kendall_matrix_set_width(int32_t width);
+int32_t tw_kendall_matrix_set_flush(int32_t k);
+int32_t tw_kendall_matrix_set_plan(int32_t max_wgs);
+int64_t tw_col_ranks_work_bytes(int32_t n_shards, int64_t total_n, int64_t max_n, int32_t p);
+int tw_col_ranks(const void* d_s, const int64_t* d_off, int32_t n_shards, int64_t total_n,
+                 int64_t max_n, int32_t p, int32_t dtype, int32_t width, void* d_work,
+                 void* d_ranks, void* stream);
+int64_t tw_kendall_matrix_work_bytes(int32_t n_shards, int32_t pa, int32_t pb);
+int tw_kendall_matrix(const void* d_ra, int32_t pa, const void* d_rb, int32_t pb,
+                      const int64_t* d_off, int32_t n_shards, int64_t max_n, int32_t width,
+                      void* d_work, int64_t* d_m, int64_t* d_ua, int64_t* d_ub, void* stream);
+
 /* ---- Two-sample triplet U-statistics of degree (2,1) (csrc/triplets.hip; tuplewise.triplets;
  * DESIGN.md §4.10; an extension, not in the reference): h = 1{D(x_i, z_k) > D(x_i, x_j)}, j != i,
  * for an anchor x_i, a point x_j of its own class and a point z_k of the other class.  d_x is

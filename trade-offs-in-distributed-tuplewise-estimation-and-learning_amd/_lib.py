@@ -303,6 +303,16 @@ _SIGNATURES = {
     "tw_dist_hist": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "tw_dist_gather": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp],
     "tw_keys_hist": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "tw_kendall_matrix_tile": [],
+    "tw_kendall_matrix_width": [_i64],
+    "tw_col_ranks_chunk": [_i64],
+    "tw_kendall_matrix_set_width": [_i32],
+    "tw_kendall_matrix_set_flush": [_i32],
+    "tw_kendall_matrix_set_plan": [_i32],
+    "tw_col_ranks_work_bytes": [_i32, _i64, _i64, _i32],
+    "tw_col_ranks": [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
+    "tw_kendall_matrix_work_bytes": [_i32, _i32, _i32],
+    "tw_kendall_matrix": [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -335,6 +345,8 @@ _RESTYPES = {
     "tw_hsic_idx_work_bytes": ctypes.c_int64,
     "tw_hsic_perm_work_bytes": ctypes.c_int64,
     "tw_dist_hist_bytes": ctypes.c_int64,
+    "tw_col_ranks_work_bytes": ctypes.c_int64,
+    "tw_kendall_matrix_work_bytes": ctypes.c_int64,
 }
 
 _lib = None
