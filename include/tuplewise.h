@@ -1293,6 +1293,40 @@ int tw_kendall_matrix(const void* d_ra, int32_t pa, const void* d_rb, int32_t pb
                       const int64_t* d_off, int32_t n_shards, int64_t max_n, int32_t width,
                       void* d_work, int64_t* d_m, int64_t* d_ua, int64_t* d_ub, void* stream);
 
+/* ---- The per-point row sums behind the variance of a Kendall tau matrix (csrc/kendall_rows.hip;
+ * tuplewise.kendall_var; an extension).  With the signs above and, for a point i
+ * of a shard,
+ *     c_i(a, b) = sum over j != i of s_a(i, j) s_b(i, j)      |c_i| <= n_s - 1
+ *     u_i(a)    = c_i(a, a)                                   the points not tied with i in a
+ * tw_kendall_rows takes ONE rank image of tw_col_ranks (d_ranks, p columns, d_off, width as
+ * tw_kendall_matrix takes them: the symmetric case only) and writes four (n_shards, p, p) int64
+ * arrays, row-major:
+ *     d_r[a, b] = sum_i c_i(a, b)              (= 2 M[a, b] of tw_kendall_matrix; d_r[a, a] = 2 U_a)
+ *     d_q[a, b] = sum_i c_i(a, b)^2
+ *     d_f[a, b] = sum_i c_i(a, b) u_i(a)       (not symmetric)
+ *     d_e[a, b] = sum_i u_i(a) u_i(b)
+ * d_r, d_q and d_e equal their transposes exactly.  A shard of fewer than 2 rows gives zeros.
+ * max_n <= 2^20 keeps every sum below 2^63.  Work items are runs of anchors i per shard and pair of
+ * 64-column groups, every anchor against all points of its shard; the integers do not depend on
+ * scheduling or on the hooks (integer atomics); the caller zeroes nothing; d_work holds
+ * tw_kendall_rows_work_bytes(n_shards, p) bytes (0 for sizes tw_kendall_rows refuses).  The
+ * diagonal groups, a partly filled last group and the pairs of groups go out as separate kernel
+ * launches, each planned by itself.  Hooks: _set_plan(max_wgs): at most max_wgs workgroups per
+ * shard and work item; _set_anchors(k): a wave carries at most k = 1, 2 or 4 anchors at once — a
+ * kernel shape whose registers do not hold k runs fewer without saying so (the hook keeps
+ * reporting k): 2 instead of 4 between two groups and at 4 column blocks of int32 ranks, and 1
+ * for the pairs with a partly filled last group in int32; the plan is sized by the anchors that
+ * run; 0 restores the default.  A hook returns the value it replaced, or -1 for a value it refuses (tw_last_error
+ * says why); both are swept by tests/test_gpu_kendall_rows.py.  Argument errors (a null buffer,
+ * n_shards < 0, p outside [1, 1024], max_n outside [0, 2^20], a width other than 16 or 32, a
+ * 16-bit image of more than 65536 rows) return TW_ERR_ARG before any launch. */
+int32_t tw_kendall_rows_set_plan(int32_t max_wgs);
+int32_t tw_kendall_rows_set_anchors(int32_t k);
+int64_t tw_kendall_rows_work_bytes(int32_t n_shards, int32_t p);
+int tw_kendall_rows(const void* d_ranks, int32_t p, const int64_t* d_off, int32_t n_shards,
+                    int64_t max_n, int32_t width, void* d_work, int64_t* d_r, int64_t* d_q,
+                    int64_t* d_f, int64_t* d_e, void* stream);
+
 /* ---- Two-sample triplet U-statistics of degree (2,1) (csrc/triplets.hip; tuplewise.triplets;
  * DESIGN.md §4.10; an extension, not in the reference): h = 1{D(x_i, z_k) > D(x_i, x_j)}, j != i,
  * for an anchor x_i, a point x_j of its own class and a point z_k of the other class.  d_x is

@@ -313,6 +313,10 @@ _SIGNATURES = {
     "tw_col_ranks": [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
     "tw_kendall_matrix_work_bytes": [_i32, _i32, _i32],
     "tw_kendall_matrix": [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "tw_kendall_rows_set_plan": [_i32],
+    "tw_kendall_rows_set_anchors": [_i32],
+    "tw_kendall_rows_work_bytes": [_i32, _i32],
+    "tw_kendall_rows": [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "tw_last_error": ctypes.c_char_p,
@@ -347,6 +351,7 @@ _RESTYPES = {
     "tw_dist_hist_bytes": ctypes.c_int64,
     "tw_col_ranks_work_bytes": ctypes.c_int64,
     "tw_kendall_matrix_work_bytes": ctypes.c_int64,
+    "tw_kendall_rows_work_bytes": ctypes.c_int64,
 }
 
 _lib = None
