@@ -1586,6 +1586,49 @@ int tw_hsic_idx32(const double* d_x, int32_t dx, const double* d_y, int32_t dy,
                   const int64_t* d_quad_off, int32_t n_shards, int64_t max_quads, int32_t kern,
                   double c_x, double c_y, void* d_work, double* d_out, void* stream);
 
+/* ---- Three row sums per point of the independence statistics above, for a grid of bandwidth
+ * pairs (csrc/hsic_rows.hip; tuplewise.hsic_var; an extension): what the
+ * first-order variance of HSIC_u / dCov^2_u is estimated from.  The partition (d_blk_off, n_blocks,
+ * max_n >= 4, blocks of any mix of sizes in one launch), dx, dy, D, g and kern are tw_hsic_sums',
+ * and the step is its own (csrc/hsictile.h), so a K_ij or L_ij has the bits tw_hsic_sums gives it.
+ * d_c holds n_sigma coefficient pairs in DEVICE memory, c_x[s] = d_c[2 s] and c_y[s] =
+ * d_c[2 s + 1], each -1 / (2 sigma^2), with n_sigma in [1, tw_hsic_rows_max_sigma()]; under
+ * TW_HSIC_DISTANCE n_sigma is 1 and d_c is not read.  With rows = d_blk_off[n_blocks] the rows
+ * the offsets span, every absolute row i inside a block gets, for every s,
+ *   d_rows[(s * rows + i) * 3 + 0] = sum over j != i of the block of K_ij L_ij
+ *   d_rows[(s * rows + i) * 3 + 1] = sum over j of K_ij wk_j     (k_i where d_w is NULL)
+ *   d_rows[(s * rows + i) * 3 + 2] = sum over j of L_ij wl_j     (l_i where d_w is NULL)
+ * (rows outside every block are not written).  d_w is NULL (wk = wl = 1.0) or the d_rows of a
+ * previous launch on the same partition and n_sigma, read at its stride of 3:
+ *   wk_j = d_w[(s * rows + j) * 3 + 2]    wl_j = d_w[(s * rows + j) * 3 + 1]
+ * and d_w[.. + 0] is not read.  So a first launch without weights gives (p, k, l) and a second one
+ * with the first's d_rows as d_w gives (p, K l, L k); d_w and d_rows must not overlap.
+ *
+ * Each unordered pair is visited once: both squared distances are evaluated once per pair and g
+ * is applied n_sigma times per side to the held values.  A pair feeds its point's sums in
+ * registers and its anchor's through a cross-lane reduce-scatter; one partial per row, tile
+ * column, sum and sigma goes to d_work (tw_hsic_rows_work_bytes bytes, nothing to zero) and a
+ * second kernel adds a row's partials in a fixed order of the columns.  No atomics; results are
+ * run-to-run deterministic, a block's rows are the same bits alone, beside other blocks and
+ * wherever the partition starts, a pair's rows do not depend on n_sigma, on its position s or on
+ * the other pairs, and [.. + 0] is the same bits with and without d_w.  Masked pairs (and their
+ * weights) are selected away, so a NaN of another block never enters; a NaN coordinate of x makes
+ * [.. + 0], [.. + 1] and, through a first launch's k as wl, the weighted [.. + 2] of its block
+ * NaN and leaves the unweighted [.. + 2] = l_i as it was.  The coefficients live on the device,
+ * so TW_HSIC_KERN_CHECKS' test of c (finite and <= 0) is the caller's.
+ *
+ * TW_ERR_ARG before any device work: a null pointer (d_w may be NULL; d_c may be NULL for the
+ * distance kernel), dx or dy outside [1, 64], an unknown kernel id, n_sigma outside
+ * [1, tw_hsic_rows_max_sigma()] or != 1 for the distance kernel, a negative size, max_n < 4 or
+ * >= 2^31, a grid past 2^31 workgroups, d_work past 1 GiB.  tw_hsic_rows_work_bytes is 0 for
+ * shapes tw_hsic_rows refuses (and for n_blocks < 1). */
+int32_t tw_hsic_rows_max_sigma(void);
+int64_t tw_hsic_rows_work_bytes(int32_t n_blocks, int64_t max_n, int32_t n_sigma);
+int tw_hsic_rows(const double* d_x, int32_t dx, const double* d_y, int32_t dy,
+                 const int64_t* d_blk_off, int32_t n_blocks, int64_t max_n, int32_t kern,
+                 const double* d_c, int32_t n_sigma, const double* d_w, void* d_work,
+                 double* d_rows, void* stream);
+
 /* ---- The permutation test of the independence statistics above (csrc/hsic_perm.hip;
  * tuplewise.hsic_perm permutation_sums / permutation_test; an extension): the
  * two of tw_hsic_sums' eight sums that a permutation of the pairing moves, for EVERY permutation

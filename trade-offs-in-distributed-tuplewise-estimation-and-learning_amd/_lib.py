@@ -293,6 +293,9 @@ _SIGNATURES = {
                      _vp],
     "tw_hsic_idx32": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f64, _f64,
                       _vp, _vp, _vp],
+    "tw_hsic_rows_max_sigma": [],
+    "tw_hsic_rows_work_bytes": [_i32, _i64, _i32],
+    "tw_hsic_rows": [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
     "tw_hsic_perm_cols": [],
     "tw_hsic_perm_work_bytes": [_i64, _i32, _i32],
     "tw_hsic_perm_sums": [_vp, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _f64, _f64, _i32,
@@ -347,6 +350,7 @@ _RESTYPES = {
     "tw_mmd_rows_work_bytes": ctypes.c_int64,
     "tw_hsic_work_bytes": ctypes.c_int64,
     "tw_hsic_idx_work_bytes": ctypes.c_int64,
+    "tw_hsic_rows_work_bytes": ctypes.c_int64,
     "tw_hsic_perm_work_bytes": ctypes.c_int64,
     "tw_dist_hist_bytes": ctypes.c_int64,
     "tw_col_ranks_work_bytes": ctypes.c_int64,
